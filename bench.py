@@ -78,6 +78,36 @@ def max_over_ranks(dist, value):
     return float(t.item())
 
 
+DUMP_CAP_BYTES = 48 * MB  # float32 on disk, all lanes of one rank together
+
+
+def dump_outputs(out_dir, got, n_objects, object_size):
+    """Write each entry of `got` ({name: read(obj, offset, nbytes) -> bytes})
+    as <out_dir>/<name>.npy in float32. A batch that fits the cap is written
+    whole; otherwise a fixed seeded sample is taken: the same slice offset in
+    every sampled object, so two builds given the same arguments dump the
+    same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_CAP_BYTES // 4 // max(len(got), 1)  # source bytes per array
+    rng = np.random.default_rng(20240229)
+    if n_objects * object_size <= budget:
+        objs = np.arange(n_objects)
+        offs = np.zeros(n_objects, dtype=np.int64)
+        chunk = object_size
+    else:
+        n_pick = min(n_objects, budget)
+        objs = np.sort(rng.choice(n_objects, size=n_pick, replace=False))
+        chunk = min(object_size, budget // n_pick)
+        offs = rng.integers(0, object_size - chunk + 1, size=n_pick)
+    for name, read in got.items():
+        parts = [np.frombuffer(read(int(i), int(o), chunk), dtype=np.uint8)
+                 for i, o in zip(objs, offs)]
+        arr = np.stack(parts).astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        log(f"dumped {name}.npy {arr.shape} (objects x bytes)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,6 +132,14 @@ def main():
                          "xGMI (launch with torchrun), 5=64KiB small-object "
                          "batches. Config 4 (tiered spill) is "
                          "scripts/bench_spill.py")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "step's gets returned as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample when the batch exceeds the cap)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (cold regime "
+                         "value_cold, multi-rank shuffle A/B, p50 get-latency "
+                         "probes); a plain run only times the steps")
     args = ap.parse_args()
     if args.preset == 1:
         args.tier, args.object_size, args.objects = "cpu", 1024, 512
@@ -248,6 +286,7 @@ def main():
         no_replace = os.environ.get("BB_BENCH_NO_REPLACE") == "1"
         cfg.replace = not no_replace
         host_sess = bb.HostPutSession()
+        last_host_get = [None]  # what the most recent batch_get returned
 
         phase_log = os.environ.get("BB_BENCH_PHASES") == "1"
 
@@ -259,6 +298,7 @@ def main():
             res = client.batch_get(keys)
             get_ms = (time.perf_counter() - t0) * 1e3
             assert all(s == 0 for s, _ in res)
+            last_host_get[0] = res
             if no_replace:
                 client.batch_remove(keys)
             if phase_log:
@@ -319,6 +359,22 @@ def main():
     elapsed = max_over_ranks(dist, elapsed)
     _gc.enable()
 
+    # ---- output dump: what the last timed step's gets handed back, before
+    # any side measurement reuses the destination buffers ----
+    if args.dump_outputs and args.steps > 0:
+        if use_gpu:
+            def fetch(L):
+                d = lane_objs[L][2]
+                return lambda i, off, n: bb.core.gpu.download(d + i * S + off, n)
+            # lanes that executed no timed step hold nothing to report
+            got = {f"rank{RANK}_lane{L}_get": fetch(L)
+                   for L in range(min(lanes, args.steps))}
+        else:
+            res = last_host_get[0]
+            got = {f"rank{RANK}_lane0_get":
+                   lambda i, off, n: bytes(res[i][1][off:off + n])}
+        dump_outputs(args.dump_outputs, got, B, S)
+
     # ---- cold regime: same workload with the placement
     # cache OFF and in-place upserts OFF — every step pays the full control
     # plane (batch_put_start allocation + batch_get_workers RPC + explicit
@@ -328,7 +384,7 @@ def main():
     # a regime SAMPLE, not a soak: cap it so huge --steps soaks don't spend
     # longer in the cold phase than the timed region
     cold_steps = max(2, min(args.steps // 4, 200))
-    if not use_gpu:
+    if args.full and not use_gpu:
         # host-tier cold regime: fresh keys, full control plane, removes
         cold_cfg = bb.PlacementConfig()
         for attr in ("replication", "checksum", "preferred_class",
@@ -353,7 +409,7 @@ def main():
         barrier(dist)
         elapsed_c = max_over_ranks(dist, time.perf_counter() - t0c)
         cold_gbps = 2.0 * B * S * cold_steps * max(WORLD, 1) / elapsed_c / 1e9
-    if use_gpu:
+    if args.full and use_gpu:
         cold_cfg = bb.PlacementConfig()
         for attr in ("replication", "checksum", "preferred_class",
                      "preferred_worker"):
@@ -408,7 +464,7 @@ def main():
         return t.item() > 0.5
 
     shuffle_ab = None
-    if use_gpu and WORLD > 1:
+    if args.full and use_gpu and WORLD > 1:
         peer = (RANK + 1) % WORLD
         peer_keys = [f"r{peer}L0o{i}" for i in range(B)]
         ab_steps = 5
@@ -486,20 +542,21 @@ def main():
     # ---- p50 single-object get latency (untimed probe, after the region) ----
     probe_us = []
     probe_key = f"r{RANK}probe"
-    if use_gpu:
+    if args.full and use_gpu:
         gcl.put_device(probe_key, src, S, cfg)
         for _ in range(args.latency_probes):
             t = time.perf_counter()
             gcl.get_device(probe_key, dst, S)
             probe_us.append((time.perf_counter() - t) * 1e6)
-    else:
+    elif args.full:
         client.put(probe_key, put_items[0][1], cfg)
         for _ in range(args.latency_probes):
             t = time.perf_counter()
             client.get(probe_key)
             probe_us.append((time.perf_counter() - t) * 1e6)
-    client.remove(probe_key)
-    p50_us = statistics.median(probe_us)
+    if args.full:
+        client.remove(probe_key)
+    p50_us = statistics.median(probe_us) if probe_us else None
 
     # whole-job application bytes: every rank puts B*S and gets B*S per step
     total_bytes = 2.0 * B * S * args.steps * max(WORLD, 1)
@@ -535,7 +592,8 @@ def main():
                 "checksum": "mfma-bbhash64" if use_gpu else "cpu-bbhash64",
                 "fused_copy": not args.no_fused_copy,
                 "pipeline_lanes": lanes,
-                "p50_get_latency_us": round(p50_us, 1),
+                "p50_get_latency_us": (round(p50_us, 1)
+                                       if p50_us is not None else None),
                 "shuffle_ab": shuffle_ab,
             },
         }

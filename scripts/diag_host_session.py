@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import blackbird_amd as bb
 cs = bb.CoordServer(); cs.start("unix:/tmp/bb-hs-coord.sock", 0)
 kc = bb.KeystoneConfig(); kc.listen_address="unix:/tmp/bb-hs-ks.sock"; kc.coord_endpoint=cs.endpoint; kc.gc_interval_ms=60000
