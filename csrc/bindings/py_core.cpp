@@ -6,6 +6,7 @@
 
 #include "blackbird/allocation/pool_allocator.h"
 #include "blackbird/allocation/range_allocator.h"
+#include "blackbird/client/batch_wire.h"
 #include "blackbird/common/result.h"
 #include "blackbird/common/types.h"
 #include "blackbird/coord/coord.h"
@@ -383,6 +384,126 @@ PYBIND11_MODULE(_core, m) {
           serde::put(e, std::vector<ShardPlacement>{sp});
           return py::bytes(e.buf);
         });
+
+  // Test-only: the v2 batch wire codec (batch_wire.h), one message per call.
+  // Values travel as dicts so the tests can hand-build them; `msg` is one of
+  // put_start2_req, put_start2_resp, get_workers2_req, get_workers2_resp,
+  // upsert_start, commit_token. Decoding a malformed body raises
+  // PROTOCOL_ERROR.
+  m.def("batch_wire_encode_for_test", [](const std::string& msg, py::dict v) {
+    struct Item {
+      std::string key;
+      uint64_t size;
+    };
+    auto placements = [&] {
+      wire::BatchPlacements p;
+      if (v.contains("view_version"))
+        p.view_version = v["view_version"].cast<uint64_t>();
+      if (v.contains("token")) p.token = v["token"].cast<uint64_t>();
+      p.pools = v["pools"].cast<std::vector<std::string>>();
+      for (auto h : v["items"]) {
+        auto it = h.cast<py::dict>();
+        wire::ItemPlaces ip;
+        ip.status = it["status"].cast<int32_t>();
+        ip.first_place = static_cast<uint32_t>(p.places.size());
+        if (it.contains("size")) ip.size = it["size"].cast<uint64_t>();
+        if (it.contains("checksum"))
+          ip.checksum = it["checksum"].cast<uint64_t>();
+        if (it.contains("places"))
+          for (auto pl : it["places"]) {
+            auto t = pl.cast<std::pair<uint16_t, uint64_t>>();
+            p.places.push_back({t.first, t.second});
+            ++ip.ncopies;
+          }
+        p.items.push_back(ip);
+      }
+      return p;
+    };
+    std::string out;
+    if (msg == "put_start2_req") {
+      std::vector<Item> items;
+      for (auto h : v["items"]) {
+        auto t = h.cast<std::pair<std::string, uint64_t>>();
+        items.push_back({t.first, t.second});
+      }
+      out = wire::encode_put_start2_request(
+          items, v["cfg"].cast<PlacementConfig>(), v["want_token"].cast<bool>());
+    } else if (msg == "put_start2_resp") {
+      out = wire::encode_put_start2_response(placements());
+    } else if (msg == "get_workers2_req") {
+      out = wire::encode_get_workers2_request(
+          v["keys"].cast<std::vector<std::string>>());
+    } else if (msg == "get_workers2_resp") {
+      out = wire::encode_get_workers2_response(placements());
+    } else if (msg == "upsert_start") {
+      out = wire::encode_upsert_start(v["token"].cast<uint64_t>());
+    } else if (msg == "commit_token") {
+      auto dg = v["digests"].cast<std::vector<uint64_t>>();
+      out = wire::encode_commit_token(v["token"].cast<uint64_t>(),
+                                      v["release"].cast<bool>(), dg.data(),
+                                      dg.size());
+    } else {
+      throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
+    }
+    return py::bytes(out);
+  });
+  m.def("batch_wire_decode_for_test",
+        [](const std::string& msg, const std::string& body, size_t nitems) {
+          py::dict v;
+          auto placements = [&](const wire::BatchPlacements& p, bool get) {
+            v["pools"] = p.pools;
+            py::list items;
+            for (auto& ip : p.items) {
+              py::dict it;
+              it["status"] = ip.status;
+              if (ip.status == 0) {
+                if (get) {
+                  it["size"] = ip.size;
+                  it["checksum"] = ip.checksum;
+                }
+                py::list places;
+                for (uint8_t c = 0; c < ip.ncopies; ++c)
+                  places.append(py::make_tuple(p.places_of(ip)[c].pool_idx,
+                                               p.places_of(ip)[c].offset));
+                it["places"] = places;
+              }
+              items.append(it);
+            }
+            v["items"] = items;
+          };
+          if (msg == "put_start2_req") {
+            auto r = unwrap(wire::decode_put_start2_request(body));
+            py::list items;
+            for (size_t i = 0; i < r.keys.size(); ++i)
+              items.append(py::make_tuple(r.keys[i], r.sizes[i]));
+            v["items"] = items;
+            v["cfg"] = r.cfg;
+            v["want_token"] = r.want_token != 0;
+          } else if (msg == "put_start2_resp") {
+            wire::BatchPlacements p;
+            unwrap_void(wire::decode_put_start2_response(body, nitems, p));
+            v["view_version"] = p.view_version;
+            v["token"] = p.token;
+            placements(p, false);
+          } else if (msg == "get_workers2_req") {
+            v["keys"] = unwrap(wire::decode_get_workers2_request(body));
+          } else if (msg == "get_workers2_resp") {
+            wire::BatchPlacements p;
+            unwrap_void(wire::decode_get_workers2_response(body, nitems, p));
+            placements(p, true);
+          } else if (msg == "upsert_start") {
+            v["token"] = unwrap(wire::decode_upsert_start(body));
+          } else if (msg == "commit_token") {
+            auto c = unwrap(wire::decode_commit_token(body));
+            v["token"] = c.token;
+            v["release"] = (c.flags & 1) != 0;
+            v["digests"] = c.digests;
+          } else {
+            throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
+          }
+          return v;
+        },
+        py::arg("msg"), py::arg("body"), py::arg("nitems") = 0);
 
   // ------------------------------------------------------------- gpu
   auto gm = m.def_submodule("gpu");

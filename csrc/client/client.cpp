@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "blackbird/client/batch_wire.h"
 #include "blackbird/client/pool_mapper.h"
 #include "blackbird/common/hex.h"
 #include "blackbird/coord/coord.h"
@@ -48,10 +49,6 @@ struct PoolsMsg {
 struct WorkersInfoMsg {
   std::vector<WorkerInfo> workers;
   BB_FIELDS(workers)
-};
-struct PutCompleteListMsg {
-  std::vector<PutCompleteRequest> reqs;
-  BB_FIELDS(reqs)
 };
 struct StatusListMsg {
   std::vector<int32_t> statuses;
@@ -573,25 +570,42 @@ Result<std::vector<int32_t>> Client::batch_put(const std::vector<PutItem>& items
                                                const PlacementConfig& cfg,
                                                HostPutSession* sess) {
   if (auto fast = try_host_session_put(items, sess)) return std::move(*fast);
-  const uint64_t gen = reconnect_gen_.load();
-  auto st = batch_put_once(items, cfg, sess);
-  if (!st.ok()) return st;
-  if (reconnect_gen_.load() == gen) return st;  // no failover: statuses final
-  // a leader change happened during the batch: redo the items whose failure
-  // is failover-shaped (the new leader lost their PENDING state) exactly once
-  std::vector<PutItem> redo;
-  std::vector<size_t> redo_idx;
-  for (size_t i = 0; i < items.size(); ++i)
-    if (failover_retriable(st.value()[i])) {
-      redo.push_back(items[i]);
-      redo_idx.push_back(i);
-    }
-  if (redo.empty()) return st;
-  auto st2 = batch_put_once(redo, cfg, nullptr);
-  if (!st2.ok()) return st;  // keep the first answer
-  for (size_t j = 0; j < redo_idx.size(); ++j)
-    st.value()[redo_idx[j]] = st2.value()[j];
-  return st;
+  return redo_after_failover(items, [&](const auto& its, bool first) {
+    return batch_put_once(its, cfg, first ? sess : nullptr);
+  });
+}
+
+// ---- put epilogues shared by the host and GPU paths (v1 and v2) ----
+
+Result<void> Client::commit_by_token(uint64_t token, bool release,
+                                     const uint64_t* digests, size_t n,
+                                     size_t stride) {
+  auto r = meta_call_raw(
+      M::BATCH_COMMIT_TOKEN,
+      wire::encode_commit_token(token, release, digests, n, stride));
+  if (!r.ok()) return r.error();
+  return {};
+}
+
+Result<void> Client::complete_by_keys(
+    const std::vector<PutCompleteRequest>& reqs,
+    const std::vector<uint32_t>& order, std::vector<int32_t>* statuses) {
+  if (reqs.empty()) return {};
+  // (a bare vector encodes exactly like a one-field list message)
+  auto r = meta_call<std::vector<PutCompleteRequest>, StatusListMsg>(
+      M::BATCH_PUT_COMPLETE, reqs);
+  if (!r.ok()) return r.error();
+  // per-item commit failures (e.g. a failover lost the PENDING state) must
+  // reach the caller, not vanish
+  if (statuses)
+    for (size_t j = 0; j < order.size() && j < r->statuses.size(); ++j)
+      if (r->statuses[j] != 0) (*statuses)[order[j]] = r->statuses[j];
+  return {};
+}
+
+void Client::cancel_puts(const std::vector<ObjectKey>& keys) {
+  if (!keys.empty())
+    meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{keys}));
 }
 
 // Token fast path for the host tier: placements unchanged since the last
@@ -612,9 +626,8 @@ std::optional<std::vector<int32_t>> Client::try_host_session_put(
       sess->token = 0;
       return std::nullopt;
     }
-  serde::Enc e1;
-  e1.num<uint64_t>(sess->token);
-  auto r1 = meta_call_raw(M::BATCH_UPSERT_START, e1.buf, opts_.rpc_timeout_ms);
+  auto r1 = meta_call_raw(M::BATCH_UPSERT_START,
+                          wire::encode_upsert_start(sess->token));
   if (!r1.ok()) {
     sess->token = 0;  // stale before any write: clean fallback
     return std::nullopt;
@@ -637,12 +650,8 @@ std::optional<std::vector<int32_t>> Client::try_host_session_put(
       }));
     for (auto& f : futs) f.get();
   }
-  serde::Enc e2;
-  e2.num<uint64_t>(sess->token);
-  e2.num<uint8_t>(0);  // keep the session
-  e2.num<uint32_t>(static_cast<uint32_t>(digests.size()));
-  for (uint64_t dg : digests) e2.num<uint64_t>(dg);
-  auto r2 = meta_call_raw(M::BATCH_COMMIT_TOKEN, e2.buf, opts_.rpc_timeout_ms);
+  auto r2 = commit_by_token(sess->token, /*release=*/false, digests.data(),
+                            digests.size());
   if (!r2.ok()) {
     sess->token = 0;  // placements changed mid-step: full path re-places
     return std::nullopt;
@@ -671,6 +680,14 @@ struct HostPoolRef {
   PoolId pool_id;
   uint8_t* base = nullptr;
   AccessInfo access;
+  ShardPlacement shard(uint64_t offset, uint64_t length) const {
+    ShardPlacement sp;
+    sp.pool_id = pool_id;
+    sp.offset = offset;
+    sp.length = length;
+    sp.access = access;
+    return sp;
+  }
 };
 }  // namespace
 
@@ -683,51 +700,29 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
     HostPutSession* sess) {
   const bool establish =
       sess != nullptr && cfg.replace && cfg.checksum && !opts_.force_tcp;
-  serde::Enc req;
-  req.num<uint32_t>(static_cast<uint32_t>(items.size()));
-  uint64_t uniform = items.empty() ? 1 : items[0].size;
-  for (auto& it : items)
-    if (it.size != uniform) { uniform = 0; break; }
-  req.num<uint64_t>(uniform);
-  if (uniform == 0)
-    for (auto& it : items) req.num<uint64_t>(it.size);
-  for (auto& it : items) req.str(it.key);
-  serde::put(req, cfg);
   const bool want_token = establish || cfg.checksum;
-  req.num<uint8_t>(want_token ? 1 : 0);
-  auto resp = meta_call_raw(M::BATCH_PUT_START2, req.buf, opts_.rpc_timeout_ms);
+  auto resp = meta_call_raw(
+      M::BATCH_PUT_START2,
+      wire::encode_put_start2_request(items, cfg, want_token));
   if (!resp.ok()) return resp.error();
-
-  serde::Dec d(resp.value().data(), resp.value().size());
-  d.num<uint64_t>();  // view version
-  const uint64_t token = d.num<uint64_t>();
-  const uint16_t npools = d.num<uint16_t>();
-  std::vector<HostPoolRef> pools(npools);
-  for (uint16_t i = 0; i < npools; ++i) {
-    pools[i].pool_id = d.str();
+  wire::BatchPlacements pl;
+  BB_RETURN_IF_ERROR(
+      wire::decode_put_start2_response(resp.value(), items.size(), pl));
+  const uint64_t token = pl.token;
+  std::vector<HostPoolRef> pools(pl.pools.size());
+  for (size_t i = 0; i < pools.size(); ++i) {
+    pools[i].pool_id = pl.pools[i];
     pools[i].base = host_pool_base(pools[i].pool_id, &pools[i].access);
   }
 
   std::vector<int32_t> statuses(items.size(), 0);
-  // per-item placement list: (pool index, offset) per copy
-  std::vector<std::vector<std::pair<uint16_t, uint64_t>>> placed(items.size());
-  for (size_t i = 0; i < items.size() && d.ok(); ++i) {
-    if (d.num<uint8_t>() != 0) {
-      statuses[i] = d.num<int32_t>();
-      continue;
-    }
-    const uint8_t ncopies = d.num<uint8_t>();
-    placed[i].reserve(ncopies);
-    for (uint8_t c = 0; c < ncopies; ++c) {
-      const uint16_t pi = d.num<uint16_t>();
-      const uint64_t off = d.num<uint64_t>();
-      if (pi >= npools)
+  for (size_t i = 0; i < items.size(); ++i) {
+    statuses[i] = pl.items[i].status;
+    // a placement naming a pool outside the table fails the item
+    for (uint8_t c = 0; c < pl.items[i].ncopies; ++c)
+      if (pl.places_of(pl.items[i])[c].pool_idx >= pools.size())
         statuses[i] = static_cast<int32_t>(ErrorCode::PROTOCOL_ERROR);
-      else
-        placed[i].emplace_back(pi, off);
-    }
   }
-  if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 response"};
 
   // establishment bookkeeping: one dst per copy per item, all host-mapped
   const uint32_t dpi = std::max<uint32_t>(cfg.replication, 1);
@@ -736,17 +731,17 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
   if (establish) {
     sess_dsts.assign(items.size() * dpi, nullptr);
     for (size_t i = 0; i < items.size() && all_mapped; ++i) {
-      if (statuses[i] != 0 || placed[i].size() != dpi) {
+      if (statuses[i] != 0 || pl.items[i].ncopies != dpi) {
         all_mapped = false;
         break;
       }
       for (uint32_t k = 0; k < dpi; ++k) {
-        HostPoolRef& pr = pools[placed[i][k].first];
-        if (!pr.base) {
+        const wire::Place& p = pl.places_of(pl.items[i])[k];
+        if (!pools[p.pool_idx].base) {
           all_mapped = false;
           break;
         }
-        sess_dsts[i * dpi + k] = pr.base + placed[i][k].second;
+        sess_dsts[i * dpi + k] = pools[p.pool_idx].base + p.offset;
       }
     }
   }
@@ -764,17 +759,14 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
         for (size_t i = next.fetch_add(1); i < items.size();
              i = next.fetch_add(1)) {
           if (statuses[i] != 0) continue;
-          for (auto& [pi, off] : placed[i]) {
-            HostPoolRef& pr = pools[pi];
+          for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
+            const wire::Place& p = pl.places_of(pl.items[i])[c];
+            HostPoolRef& pr = pools[p.pool_idx];
             if (pr.base) {
-              std::memcpy(pr.base + off, items[i].data, items[i].size);
+              std::memcpy(pr.base + p.offset, items[i].data, items[i].size);
             } else {
-              ShardPlacement sp;
-              sp.pool_id = pr.pool_id;
-              sp.offset = off;
-              sp.length = items[i].size;
-              sp.access = pr.access;
-              auto r = write_shard(sp, items[i].data);
+              auto r = write_shard(pr.shard(p.offset, items[i].size),
+                                   items[i].data);
               if (!r.ok()) {
                 statuses[i] = static_cast<int32_t>(r.code());
                 break;
@@ -792,16 +784,10 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
   for (auto st : statuses)
     if (st != 0) { all_ok = false; break; }
   const bool keep_session = all_ok && establish && all_mapped;
-  bool committed = false;
-  if (all_ok) {
-    serde::Enc e2;
-    e2.num<uint64_t>(token);
-    e2.num<uint8_t>(keep_session ? 0 : 1);  // one-shot unless establishing
-    e2.num<uint32_t>(static_cast<uint32_t>(digests.size()));
-    for (uint64_t dg : digests) e2.num<uint64_t>(dg);
-    committed =
-        meta_call_raw(M::BATCH_COMMIT_TOKEN, e2.buf, opts_.rpc_timeout_ms).ok();
-  }
+  // one-shot unless establishing
+  const bool committed =
+      all_ok && commit_by_token(token, /*release=*/!keep_session,
+                                digests.data(), digests.size()).ok();
   if (keep_session && committed) {
     sess->token = token;
     sess->descs_per_item = dpi;
@@ -819,9 +805,9 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
     sess->token = 0;
   }
   if (!committed) {
-    PutCompleteListMsg completes;
-    std::vector<std::string> cancels;
-    std::vector<size_t> complete_idx;
+    std::vector<PutCompleteRequest> completes;
+    std::vector<ObjectKey> cancels;
+    std::vector<uint32_t> complete_idx;
     for (size_t i = 0; i < items.size(); ++i) {
       if (statuses[i] != 0) {
         if (statuses[i] != static_cast<int32_t>(ErrorCode::OBJECT_EXISTS) &&
@@ -829,19 +815,11 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
           cancels.push_back(items[i].key);
         continue;
       }
-      completes.reqs.push_back(PutCompleteRequest{items[i].key, digests[i], {}});
-      complete_idx.push_back(i);
+      completes.push_back(PutCompleteRequest{items[i].key, digests[i], {}});
+      complete_idx.push_back(static_cast<uint32_t>(i));
     }
-    if (!completes.reqs.empty()) {
-      auto r = meta_call<PutCompleteListMsg, StatusListMsg>(
-          M::BATCH_PUT_COMPLETE, completes, opts_.rpc_timeout_ms);
-      if (!r.ok()) return r.error();
-      for (size_t j = 0; j < complete_idx.size() && j < r->statuses.size(); ++j)
-        if (r->statuses[j] != 0) statuses[complete_idx[j]] = r->statuses[j];
-    }
-    if (!cancels.empty())
-      meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{cancels}),
-                    opts_.rpc_timeout_ms);
+    BB_RETURN_IF_ERROR(complete_by_keys(completes, complete_idx, &statuses));
+    cancel_puts(cancels);
   }
   return statuses;
 }
@@ -849,43 +827,25 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
 Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once_v2(
     const std::vector<ObjectKey>& keys, bool* fallback) {
   *fallback = false;
-  serde::Enc req;
-  req.num<uint32_t>(static_cast<uint32_t>(keys.size()));
-  for (auto& k : keys) req.str(k);
-  auto resp =
-      meta_call_raw(M::BATCH_GET_WORKERS2, req.buf, opts_.rpc_timeout_ms);
+  auto resp = meta_call_raw(M::BATCH_GET_WORKERS2,
+                            wire::encode_get_workers2_request(keys));
   if (!resp.ok()) return resp.error();
-
-  serde::Dec d(resp.value().data(), resp.value().size());
-  const uint16_t npools = d.num<uint16_t>();
-  std::vector<HostPoolRef> pools(npools);
-  for (uint16_t i = 0; i < npools; ++i) {
-    pools[i].pool_id = d.str();
+  wire::BatchPlacements pl;
+  BB_RETURN_IF_ERROR(
+      wire::decode_get_workers2_response(resp.value(), keys.size(), pl));
+  std::vector<HostPoolRef> pools(pl.pools.size());
+  for (size_t i = 0; i < pools.size(); ++i) {
+    pools[i].pool_id = pl.pools[i];
     pools[i].base = host_pool_base(pools[i].pool_id, &pools[i].access);
   }
 
   std::vector<std::pair<int32_t, std::string>> out(keys.size());
-  std::vector<uint64_t> want(keys.size(), 0);
-  std::vector<std::vector<std::pair<uint16_t, uint64_t>>> copies(keys.size());
-  for (size_t i = 0; i < keys.size() && d.ok(); ++i) {
-    if (d.num<uint8_t>() != 0) {
-      out[i].first = d.num<int32_t>();
-      if (out[i].first == static_cast<int32_t>(ErrorCode::NOT_IMPLEMENTED))
-        *fallback = true;  // striped object in the batch: run the v1 path
-      continue;
-    }
-    const uint64_t size = d.num<uint64_t>();
-    want[i] = d.num<uint64_t>();
-    out[i].second.resize(size);
-    const uint8_t ncopies = d.num<uint8_t>();
-    copies[i].reserve(ncopies);
-    for (uint8_t c = 0; c < ncopies; ++c) {
-      const uint16_t pi = d.num<uint16_t>();
-      const uint64_t off = d.num<uint64_t>();
-      if (pi < npools) copies[i].emplace_back(pi, off);
-    }
+  for (size_t i = 0; i < keys.size(); ++i) {
+    out[i].first = pl.items[i].status;
+    if (out[i].first == static_cast<int32_t>(ErrorCode::NOT_IMPLEMENTED))
+      *fallback = true;  // striped object in the batch: run the v1 path
+    if (out[i].first == 0) out[i].second.resize(pl.items[i].size);
   }
-  if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 response"};
   if (*fallback) return out;
 
   std::atomic<size_t> next{0};
@@ -900,23 +860,21 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once_v2(
         const uint64_t size = out[i].second.size();
         Error last{ErrorCode::NO_PLACEMENT, "no copies"};
         bool done = false;
-        for (auto& [pi, off] : copies[i]) {
-          HostPoolRef& pr = pools[pi];
+        const uint64_t want = pl.items[i].checksum;
+        for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
+          const wire::Place& p = pl.places_of(pl.items[i])[c];
+          if (p.pool_idx >= pools.size()) continue;  // unknown pool: skip copy
+          HostPoolRef& pr = pools[p.pool_idx];
           if (pr.base) {
-            std::memcpy(out[i].second.data(), pr.base + off, size);
+            std::memcpy(out[i].second.data(), pr.base + p.offset, size);
             done = true;
           } else {
-            ShardPlacement sp;
-            sp.pool_id = pr.pool_id;
-            sp.offset = off;
-            sp.length = size;
-            sp.access = pr.access;
-            auto r = read_shard(sp, out[i].second.data());
+            auto r = read_shard(pr.shard(p.offset, size), out[i].second.data());
             if (r.ok()) done = true;
             else last = r.error();
           }
-          if (done && opts_.verify_checksum_on_get && want[i] != 0) {
-            if (gpu::checksum_cpu(out[i].second.data(), size) != want[i]) {
+          if (done && opts_.verify_checksum_on_get && want != 0) {
+            if (gpu::checksum_cpu(out[i].second.data(), size) != want) {
               done = false;  // corrupt copy: try the next one
               last = Error{ErrorCode::CHECKSUM_MISMATCH, keys[i]};
             }
@@ -948,6 +906,29 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
 
   std::vector<int32_t> statuses(items.size(), 0);
   std::vector<uint64_t> digests(items.size(), 0);
+  // epilogue of both transfer strategies below: complete what transferred
+  // (striped copies carry per-shard digests), cancel what did not
+  auto finish = [&]() -> Result<std::vector<int32_t>> {
+    std::vector<PutCompleteRequest> completes;
+    std::vector<ObjectKey> cancels;
+    std::vector<uint32_t> complete_idx;
+    for (size_t i = 0; i < items.size(); ++i) {
+      if (start->items[i].status != 0) continue;  // placement failed
+      if (statuses[i] != 0) {
+        cancels.push_back(items[i].key);
+        continue;
+      }
+      PutCompleteRequest pc{items[i].key, digests[i], {}};
+      if (cfg.checksum)
+        pc.shard_digests =
+            host_shard_digests(start->items[i].copies, items[i].data);
+      completes.push_back(std::move(pc));
+      complete_idx.push_back(static_cast<uint32_t>(i));
+    }
+    BB_RETURN_IF_ERROR(complete_by_keys(completes, complete_idx, &statuses));
+    cancel_puts(cancels);
+    return statuses;
+  };
 
   if (opts_.force_tcp) {
     // one DATA_BATCH_WRITE per worker endpoint instead of one RPC per shard
@@ -992,36 +973,7 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
         for (size_t i = 0; i < items.size(); ++i)
           if (statuses[i] == 0 && start->items[i].status == 0)
             digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
-      PutCompleteListMsg completes2;
-      std::vector<std::string> cancels2;
-      std::vector<size_t> complete_idx2;
-      for (size_t i = 0; i < items.size(); ++i) {
-        if (start->items[i].status != 0) continue;
-        if (statuses[i] != 0) {
-          cancels2.push_back(items[i].key);
-          continue;
-        }
-        PutCompleteRequest pc{items[i].key, digests[i], {}};
-        if (cfg.checksum)
-          pc.shard_digests =
-              host_shard_digests(start->items[i].copies, items[i].data);
-        completes2.reqs.push_back(std::move(pc));
-        complete_idx2.push_back(i);
-      }
-      if (!completes2.reqs.empty()) {
-        auto r = meta_call<PutCompleteListMsg, StatusListMsg>(
-            M::BATCH_PUT_COMPLETE, completes2, opts_.rpc_timeout_ms);
-        if (!r.ok()) return r.error();
-        // per-item commit failures (e.g. a failover lost the PENDING state)
-        // must reach the caller, not vanish
-        for (size_t j = 0; j < complete_idx2.size() &&
-                           j < r->statuses.size(); ++j)
-          if (r->statuses[j] != 0) statuses[complete_idx2[j]] = r->statuses[j];
-      }
-      if (!cancels2.empty())
-        meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{cancels2}),
-                       opts_.rpc_timeout_ms);
-      return statuses;
+      return finish();
     }
   }
 
@@ -1051,55 +1003,15 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
       }));
     for (auto& f : futs) f.get();
   }
-  PutCompleteListMsg completes;
-  std::vector<std::string> cancels;
-  std::vector<size_t> complete_idx;
-  for (size_t i = 0; i < items.size(); ++i) {
-    if (start->items[i].status != 0) continue;  // placement failed
-    if (statuses[i] != 0) {
-      cancels.push_back(items[i].key);
-      continue;
-    }
-    PutCompleteRequest pc{items[i].key, digests[i], {}};
-    if (cfg.checksum)
-      pc.shard_digests =
-          host_shard_digests(start->items[i].copies, items[i].data);
-    completes.reqs.push_back(std::move(pc));
-    complete_idx.push_back(i);
-  }
-  if (!completes.reqs.empty()) {
-    auto r = meta_call<PutCompleteListMsg, StatusListMsg>(
-        M::BATCH_PUT_COMPLETE, completes, opts_.rpc_timeout_ms);
-    if (!r.ok()) return r.error();
-    for (size_t j = 0; j < complete_idx.size() && j < r->statuses.size(); ++j)
-      if (r->statuses[j] != 0) statuses[complete_idx[j]] = r->statuses[j];
-  }
-  if (!cancels.empty())
-    meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{cancels}),
-                   opts_.rpc_timeout_ms);
-  return statuses;
+  return finish();
 }
 
 Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get(
     const std::vector<ObjectKey>& keys) {
-  const uint64_t gen = reconnect_gen_.load();
-  auto out = batch_get_once(keys);
-  if (!out.ok() || reconnect_gen_.load() == gen) return out;
   // failover mid-batch: the new leader may briefly lag the persistence
-  // stream — redo failover-shaped per-item failures once
-  std::vector<ObjectKey> redo;
-  std::vector<size_t> redo_idx;
-  for (size_t i = 0; i < keys.size(); ++i)
-    if (failover_retriable(out.value()[i].first)) {
-      redo.push_back(keys[i]);
-      redo_idx.push_back(i);
-    }
-  if (redo.empty()) return out;
-  auto out2 = batch_get_once(redo);
-  if (!out2.ok()) return out;
-  for (size_t j = 0; j < redo_idx.size(); ++j)
-    out.value()[redo_idx[j]] = std::move(out2.value()[j]);
-  return out;
+  // stream — failover-shaped per-item failures are redone once
+  return redo_after_failover(
+      keys, [&](const auto& ks, bool) { return batch_get_once(ks); });
 }
 
 Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once(

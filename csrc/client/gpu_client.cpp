@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "blackbird/client/batch_wire.h"
 #include "blackbird/client/pool_mapper.h"
 #include "blackbird/common/trace.h"
 #include "blackbird/common/log.h"
@@ -41,14 +42,11 @@ struct KeysMsg {
   std::vector<std::string> keys;
   BB_FIELDS(keys)
 };
-struct PutCompleteListMsg {
-  std::vector<PutCompleteRequest> reqs;
-  BB_FIELDS(reqs)
-};
-struct StatusListMsg {
-  std::vector<int32_t> statuses;
-  BB_FIELDS(statuses)
-};
+
+bool aligned16(const void* a, const void* b = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) &
+          15) == 0;
+}
 }  // namespace
 
 GpuClient::GpuClient(Client& base, int device) : c_(base), device_(device) {}
@@ -106,88 +104,283 @@ Result<void> GpuClient::init() {
   return {};
 }
 
-GpuClient::Resolved GpuClient::resolve_device_ptr(const ShardPlacement& s) {
-  bool is_dev = false;
-  int dev = -1;
-  uint64_t pool_size = 0;
-  if (void* base = LocalPools::inst().lookup(s.pool_id, &is_dev, &dev,
-                                             &pool_size)) {
-    if (is_dev)
-      return {static_cast<uint8_t*>(base) + s.offset, dev == device_};
-    // host pool in this process (pinned/shm tier): pin+map once so the GPU
-    // addresses it directly (PCIe DMA) instead of staging through a bounce
-    if (void* dm = c_.mapper_->host_dev_map(s.pool_id, base, pool_size))
-      return {static_cast<uint8_t*>(dm) + s.offset, false};
-    return {};  // unmappable host pool: staged path
-  }
-  AccessInfo a = s.access;
-  if (a.endpoint.empty()) {
-    auto r = c_.pool_access(s.pool_id);
-    if (!r.ok()) return {};
-    a = std::move(r.value());
-  }
-  if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
-    // host pool of ANOTHER process: shm-map it, then GPU-map the mapping
-    uint64_t sz = 0;
-    if (void* base = c_.mapper_->map_shm(a.shm_name, 0, &sz))
-      if (void* dm = c_.mapper_->host_dev_map(s.pool_id, base, sz))
-        return {static_cast<uint8_t*>(dm) + s.offset, false};
-    return {};
-  }
-  if (a.kind != AccessKind::HIP_IPC || a.ipc_handle_hex.empty()) return {};
-  void* base = c_.mapper_->open_ipc(a.ipc_handle_hex, a.device_id);
-  if (!base) return {};
-  // IPC pools come from other processes (one rank per GPU) ⇒ cross-device
-  return {static_cast<uint8_t*>(base) + s.offset, false};
-}
-
-// Shared pool-table resolution for the v2 batch protocols: device-visible
-// base (HBM local, IPC peer, or GPU-mapped host tier) or nullptr (staged).
+// Device-visible base of a pool — HBM local, IPC peer, or GPU-mapped host
+// tier — or nullptr (staged path). `hint` is access info the caller already
+// holds (a v1 shard carries it): with an endpoint in it no pool_access RPC
+// is issued.
 uint8_t* GpuClient::resolve_pool_base(const PoolId& pool_id, AccessInfo* access,
-                                      bool* same_device) {
+                                      const AccessInfo* hint) {
   bool is_dev = false;
   int dev = -1;
   uint64_t pool_size = 0;
   if (void* base = LocalPools::inst().lookup(pool_id, &is_dev, &dev,
                                              &pool_size)) {
-    if (is_dev) {
-      if (same_device) *same_device = dev == device_;
-      return static_cast<uint8_t*>(base);
-    }
+    if (is_dev) return static_cast<uint8_t*>(base);
+    // host pool in this process (pinned/shm tier): pin+map once so the GPU
+    // addresses it directly (PCIe DMA) instead of staging through a bounce
     return static_cast<uint8_t*>(
         c_.mapper_->host_dev_map(pool_id, base, pool_size));
   }
-  auto a = c_.pool_access(pool_id);
-  if (!a.ok()) return nullptr;
+  AccessInfo a;
+  if (hint && !hint->endpoint.empty()) {
+    a = *hint;
+  } else {
+    auto r = c_.pool_access(pool_id);
+    if (!r.ok()) return nullptr;
+    a = std::move(r.value());
+  }
   uint8_t* out = nullptr;
-  if (a->kind == AccessKind::HIP_IPC && !a->ipc_handle_hex.empty()) {
+  if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty()) {
+    // IPC pools come from other processes (one rank per GPU)
     out = static_cast<uint8_t*>(
-        c_.mapper_->open_ipc(a->ipc_handle_hex, a->device_id));
-  } else if (a->kind == AccessKind::SHM && !a->shm_name.empty()) {
+        c_.mapper_->open_ipc(a.ipc_handle_hex, a.device_id));
+  } else if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
+    // host pool of ANOTHER process: shm-map it, then GPU-map the mapping
     uint64_t sz = 0;
-    if (void* base = c_.mapper_->map_shm(a->shm_name, 0, &sz))
+    if (void* base = c_.mapper_->map_shm(a.shm_name, 0, &sz))
       out = static_cast<uint8_t*>(c_.mapper_->host_dev_map(pool_id, base, sz));
   }
-  if (access) *access = std::move(a.value());
+  if (access) *access = std::move(a);
   return out;
+}
+
+uint8_t* GpuClient::resolve_device_ptr(const ShardPlacement& s) {
+  uint8_t* base = resolve_pool_base(s.pool_id, nullptr, &s.access);
+  return base ? base + s.offset : nullptr;
+}
+
+// One pool-table entry of a v2 response, resolved once per batch.
+struct GpuClient::PoolRef {
+  PoolId pool_id;
+  uint8_t* base = nullptr;  // device-visible base or nullptr
+  AccessInfo access;        // for the staged fallback
+};
+
+std::vector<GpuClient::PoolRef> GpuClient::resolve_pools(
+    const std::vector<PoolId>& ids) {
+  std::vector<PoolRef> pools(ids.size());
+  for (size_t i = 0; i < ids.size(); ++i) {
+    pools[i].pool_id = ids[i];
+    pools[i].base = resolve_pool_base(ids[i], &pools[i].access);
+  }
+  return pools;
+}
+
+// Routes the (user buffer ↔ pool range) transfers of one batch: a
+// device-visible range joins the fused copy list (one kernel launch at
+// flush()) or, with fused copies off, goes out as hipMemcpyAsync on the
+// rotating streams; a range that is not device-visible is staged through
+// pinned host memory — queued for the caller's fan-out (v2 batches), or done
+// on the spot (v1 paths, whose shards are few and large).
+template <bool Put>
+struct GpuClient::Router {
+  using User = std::conditional_t<Put, const uint8_t*, uint8_t*>;
+  using StagedPtr = std::conditional_t<Put, const void*, void*>;
+
+  GpuClient& g;
+  const bool fused;
+  const bool defer_staged;
+  std::vector<gpu::CopyDesc> copies;  // fused copy list
+  int si = 0;                         // SDMA copies issued (stream rotation)
+  std::vector<std::pair<ShardPlacement, StagedPtr>> staged;
+  std::vector<uint32_t> staged_idx;   // item of staged[k]
+  // items that bypass add(): they ride the copy+digest kernel instead
+  std::vector<gpu::PutDesc> hashed;
+  std::vector<uint32_t> hashed_idx;
+  std::vector<uint32_t> plain_idx;    // items moved by add() alone
+  std::vector<uint64_t> hashed_digests, plain_digests;  // launch_put() output
+
+  Router(GpuClient& gc, bool fused_copy, bool defer)
+      : g(gc), fused(fused_copy), defer_staged(defer) {}
+
+  // v1: one shard, already resolved (pool_ptr nullptr = not device-visible)
+  Result<void> add(User user, uint8_t* pool_ptr, const ShardPlacement& s,
+                   uint32_t item) {
+    if (pool_ptr) return direct(user, pool_ptr, s.length);
+    return stage(s, user, item);
+  }
+  // v1: every shard of one copy, back to back in the user buffer
+  Result<void> add_copy(User user, const CopyPlacement& copy, uint32_t item) {
+    for (const auto& s : copy.shards) {
+      BB_RETURN_IF_ERROR(add(user, g.resolve_device_ptr(s), s, item));
+      user += s.length;
+    }
+    return {};
+  }
+  // v2: a range of a pool-table entry
+  Result<void> add(User user, const PoolRef& pr, uint64_t offset,
+                   uint64_t nbytes, uint32_t item) {
+    if (pr.base) return direct(user, pr.base + offset, nbytes);
+    ShardPlacement sp;
+    sp.pool_id = pr.pool_id;
+    sp.offset = offset;
+    sp.length = nbytes;
+    sp.access = pr.access;
+    return stage(std::move(sp), user, item);
+  }
+
+  // launch the fused copy list on streams_[0]
+  Result<void> flush() {
+    if (copies.empty()) return {};
+    return gpu::batched_copy(copies.data(),
+                             static_cast<uint32_t>(copies.size()),
+                             g.streams_[0]);
+  }
+  // the copy+digest list on streams_[2] (synchronizes that stream itself)
+  Result<std::vector<uint64_t>> run_hashed() {
+    std::vector<uint64_t> digests(hashed.size(), 0);
+    BB_RETURN_IF_ERROR(gpu::fused_put(hashed.data(),
+                                      static_cast<uint32_t>(hashed.size()),
+                                      digests.data(), g.streams_[2]));
+    return digests;
+  }
+  // Everything a put batch launches, in order: the copy list (stream 0), one
+  // digest launch over the SOURCE buffers of the plain items (stream 1, so
+  // it overlaps the SDMA copies), the copy+digest list (stream 2); then the
+  // sync. Fills plain_digests / hashed_digests.
+  Result<void> launch_put(const std::vector<DevPutItem>& items, bool checksum) {
+    BB_RETURN_IF_ERROR(flush());
+    plain_digests.assign(plain_idx.size(), 0);
+    if (checksum) {
+      auto r = g.digest_items(
+          plain_idx, [&](uint32_t i) { return items[i].ptr; },
+          [&](uint32_t i) { return items[i].size; }, g.streams_[1]);
+      if (!r.ok()) return r.error();
+      plain_digests = std::move(r.value());
+    }
+    auto r = run_hashed();
+    if (!r.ok()) return r.error();
+    hashed_digests = std::move(r.value());
+    return sync();
+  }
+  // Everything a get batch launches after routing: the copy list (stream
+  // 0), the copy+digest list (stream 2; verifies as it gathers), the sync,
+  // then with `verify` one digest launch over what the plain items fetched
+  // (stream 0). meta_of(i) → {size, recorded checksum (0 = none)} of item i.
+  template <typename MetaOf>
+  Result<void> finish_get(const std::vector<DevGetItem>& items, bool verify,
+                          MetaOf meta_of, std::vector<int32_t>& statuses) {
+    auto check = [&](const std::vector<uint32_t>& idx,
+                     const std::vector<uint64_t>& got, bool zero_passes) {
+      for (size_t j = 0; j < idx.size(); ++j) {
+        const uint64_t want = meta_of(idx[j]).second;
+        if (got[j] != want && !(zero_passes && want == 0))
+          statuses[idx[j]] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
+      }
+    };
+    BB_RETURN_IF_ERROR(flush());
+    auto hashed_got = run_hashed();
+    if (!hashed_got.ok()) return hashed_got.error();
+    check(hashed_idx, hashed_got.value(), false);
+    BB_RETURN_IF_ERROR(sync());
+    if (!verify) return {};
+    auto got = g.digest_items(
+        plain_idx, [&](uint32_t i) { return items[i].ptr; },
+        [&](uint32_t i) { return meta_of(i).first; }, g.streams_[0]);
+    if (!got.ok()) return got.error();
+    check(plain_idx, got.value(), true);
+    return {};
+  }
+  // only streams that carried work: stream 0 (fused list) and the first
+  // `si` rotating SDMA streams (checksum_batch and fused_put synchronize
+  // their own streams internally)
+  Result<void> sync() {
+    if (!copies.empty()) BB_HIP(hipStreamSynchronize(g.streams_[0]));
+    for (int j = 0; j < std::min(si, kStreams); ++j)
+      BB_HIP(hipStreamSynchronize(g.streams_[j]));
+    return {};
+  }
+
+ private:
+  Result<void> direct(User user, uint8_t* pool_ptr, uint64_t nbytes) {
+    const void* src = Put ? static_cast<const void*>(user) : pool_ptr;
+    void* dst = Put ? static_cast<void*>(pool_ptr)
+                    : const_cast<uint8_t*>(user);
+    if (fused) {
+      copies.push_back({src, dst, nbytes});
+      return {};
+    }
+    BB_HIP(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToDevice,
+                          g.streams_[si % kStreams]));
+    ++si;
+    return {};
+  }
+  template <typename Shard>
+  Result<void> stage(Shard&& s, User user, uint32_t item) {
+    if (defer_staged) {
+      staged.emplace_back(std::forward<Shard>(s), user);
+      staged_idx.push_back(item);
+      return {};
+    }
+    if constexpr (Put) return g.staged_write(s, user);
+    else return g.staged_read(s, user);
+  }
+};
+
+// One batched digest launch over items[indices]: out[j] is the digest of
+// ptr_of(indices[j]) .. + size_of(indices[j]). No launch for an empty list.
+template <typename PtrOf, typename SizeOf>
+Result<std::vector<uint64_t>> GpuClient::digest_items(
+    const std::vector<uint32_t>& indices, PtrOf ptr_of, SizeOf size_of,
+    hipStream_t stream) {
+  std::vector<uint64_t> out(indices.size(), 0);
+  if (indices.empty()) return out;
+  std::vector<const void*> ptrs;
+  std::vector<uint64_t> sizes;
+  ptrs.reserve(indices.size());
+  sizes.reserve(indices.size());
+  for (auto i : indices) {
+    ptrs.push_back(ptr_of(i));
+    sizes.push_back(size_of(i));
+  }
+  BB_RETURN_IF_ERROR(gpu::checksum_batch(ptrs.data(), sizes.data(),
+                                         static_cast<uint32_t>(ptrs.size()),
+                                         out.data(), device_, stream));
+  return out;
+}
+
+// BATCH_PUT_COMPLETE for what a put batch transferred: the plain group
+// (skipping items a failed staged write marked) and the copy+digest group,
+// whose digests sit `stride` apart (one per replica). v1 attaches per-shard
+// digests and applies the per-item answers; v2 does neither.
+Result<void> GpuClient::complete_puts(
+    const std::vector<DevPutItem>& items, const Router<true>& rt, size_t stride,
+    std::map<uint32_t, std::vector<std::vector<uint64_t>>>* shard_digests,
+    std::vector<int32_t>& statuses, bool apply_statuses) {
+  std::vector<PutCompleteRequest> reqs;
+  std::vector<uint32_t> order;
+  for (size_t j = 0; j < rt.plain_idx.size(); ++j) {
+    const uint32_t i = rt.plain_idx[j];
+    if (statuses[i] != 0) continue;
+    PutCompleteRequest pc{items[i].key, rt.plain_digests[j], {}};
+    if (shard_digests)
+      if (auto it = shard_digests->find(i); it != shard_digests->end())
+        pc.shard_digests = std::move(it->second);
+    reqs.push_back(std::move(pc));
+    order.push_back(i);
+  }
+  for (size_t j = 0; j < rt.hashed_idx.size(); ++j) {
+    reqs.push_back(PutCompleteRequest{items[rt.hashed_idx[j]].key,
+                                      rt.hashed_digests[j * stride], {}});
+    order.push_back(rt.hashed_idx[j]);
+  }
+  return c_.complete_by_keys(reqs, order, apply_statuses ? &statuses : nullptr);
+}
+
+// BATCH_PUT_CANCEL for the items whose transfer failed
+void GpuClient::cancel_failed(const std::vector<DevPutItem>& items,
+                              const std::vector<int32_t>& statuses) {
+  std::vector<ObjectKey> cancels;
+  for (size_t i = 0; i < items.size(); ++i)
+    if (statuses[i] == static_cast<int32_t>(ErrorCode::TRANSFER_FAILED))
+      cancels.push_back(items[i].key);
+  c_.cancel_puts(cancels);
 }
 
 Result<void> GpuClient::staged_write(const ShardPlacement& s, const void* dev_src) {
   // D2H into pinned staging, then the host path (SHM memcpy or TCP frame).
   std::lock_guard<std::mutex> g(staging_mu_);  // async batches share staging_
-  uint64_t done = 0;
-  while (done < s.length) {
-    uint64_t chunk = std::min(s.length - done, staging_size_);
-    BB_RETURN_IF_ERROR(gpu::copy_sync(
-        staging_, static_cast<const uint8_t*>(dev_src) + done, chunk,
-        hipMemcpyDeviceToHost));
-    ShardPlacement part = s;
-    part.offset = s.offset + done;
-    part.length = chunk;
-    BB_RETURN_IF_ERROR(c_.write_shard(part, staging_));
-    done += chunk;
-  }
-  return {};
+  return staged_write_buf(s, dev_src, staging_, staging_size_);
 }
 
 Result<void> GpuClient::staged_read_buf(const ShardPlacement& s, void* dev_dst,
@@ -364,33 +557,15 @@ Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
 
   Error last{ErrorCode::NO_PLACEMENT, "no copies"};
   for (const auto& copy : meta->copies) {
-    uint64_t off = 0;
-    bool ok = true;
-    int si = 0;
-    for (const auto& s : copy.shards) {
-      if (void* src = resolve_device_ptr(s).ptr) {
-        hipError_t e = hipMemcpyAsync(static_cast<uint8_t*>(dev_ptr) + off, src,
-                                      s.length, hipMemcpyDeviceToDevice,
-                                      streams_[si % kStreams]);
-        if (e != hipSuccess) {
-          ok = false;
-          last = hip_err(e, "hipMemcpyAsync get");
-          break;
-        }
-      } else {
-        auto r = staged_read(s, static_cast<uint8_t*>(dev_ptr) + off);
-        if (!r.ok()) {
-          ok = false;
-          last = r.error();
-          break;
-        }
-      }
-      off += s.length;
-      ++si;
+    // one object: always plain copies on the rotating streams (a kernel
+    // launch costs more than it saves here), staged shards on the spot
+    Router<false> rt(*this, /*fused_copy=*/false, /*defer=*/false);
+    auto r = rt.add_copy(static_cast<uint8_t*>(dev_ptr), copy, 0);
+    BB_RETURN_IF_ERROR(rt.sync());
+    if (!r.ok()) {
+      last = r.error();
+      continue;
     }
-    const int used = std::min<int>(si, kStreams);
-    for (int k = 0; k < used; ++k) BB_HIP(hipStreamSynchronize(streams_[k]));
-    if (!ok) continue;
     if (verify && meta->checksum != 0) {
       auto cs = gpu::checksum_sync(dev_ptr, meta->size, device_, streams_[0]);
       if (!cs.ok()) return cs.error();
@@ -406,15 +581,6 @@ Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
 // ------------------------ compact v2 batch protocol ------------------------
 // Pool-table responses with fixed-width placements: the client resolves each
 // POOL once (not each object) and decodes with zero per-item allocations.
-
-namespace {
-struct PoolRef {
-  std::string pool_id;
-  uint8_t* base = nullptr;   // device-visible base or nullptr
-  bool same_device = false;
-  AccessInfo access;         // for the staged fallback
-};
-}  // namespace
 
 template <typename Sess>
 Result<void> GpuClient::session_kernel(Sess* sess, uint64_t* digests) {
@@ -475,9 +641,8 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
   // RPC 1 (8 bytes): flip the session's objects to PENDING — placements are
   // now pinned (tiering/eviction/repair only touch COMMITTED objects), so
   // the one-sided writes below cannot race a migration
-  serde::Enc e1;
-  e1.num<uint64_t>(sess->token);
-  auto r1 = c_.meta_call_raw(M::BATCH_UPSERT_START, e1.buf);
+  auto r1 = c_.meta_call_raw(M::BATCH_UPSERT_START,
+                             wire::encode_upsert_start(sess->token));
   if (!r1.ok()) {
     sess->token = 0;  // stale/error before any write: clean fallback
     return std::nullopt;
@@ -485,14 +650,10 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
   std::vector<uint64_t> digests(sess->descs.size(), 0);
   auto rk = session_kernel(sess, digests.data());
   if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
-  serde::Enc e2;
-  e2.num<uint64_t>(sess->token);
-  e2.num<uint8_t>(0);  // keep the session for the next step
-  e2.num<uint32_t>(static_cast<uint32_t>(items.size()));
-  // one digest per ITEM (replicas hash identical bytes; take copy 0's)
-  for (size_t i = 0; i < items.size(); ++i)
-    e2.num<uint64_t>(digests[i * dpi]);
-  auto r2 = c_.meta_call_raw(M::BATCH_COMMIT_TOKEN, e2.buf);
+  // keep the session for the next step; one digest per ITEM (replicas hash
+  // identical bytes; take copy 0's)
+  auto r2 = c_.commit_by_token(sess->token, /*release=*/false, digests.data(),
+                               items.size(), dpi);
   if (!r2.ok()) {
     // placements changed mid-step (rare): fall back — the full path
     // re-places and rewrites the batch
@@ -526,232 +687,93 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
   // of re-sending every key in BATCH_PUT_COMPLETE (released at commit)
   const bool want_token = establish || (cfg.checksum && fused_copy_);
   const uint32_t dpi = std::max<uint32_t>(cfg.replication, 1);
-  serde::Enc req;
-  req.num<uint32_t>(static_cast<uint32_t>(items.size()));
-  // uniform size when possible (the common batched pattern)
-  uint64_t uniform = items.empty() ? 1 : items[0].size;
-  for (auto& it : items)
-    if (it.size != uniform) { uniform = 0; break; }
-  req.num<uint64_t>(uniform);
-  if (uniform == 0)
-    for (auto& it : items) req.num<uint64_t>(it.size);
-  for (auto& it : items) req.str(it.key);
-  serde::put(req, cfg);
-  req.num<uint8_t>(want_token ? 1 : 0);
-  auto resp = c_.meta_call_raw(rpc::methods::BATCH_PUT_START2, req.buf);
+  auto resp = c_.meta_call_raw(
+      M::BATCH_PUT_START2,
+      wire::encode_put_start2_request(items, cfg, want_token));
   if (!resp.ok()) return resp.error();
-
-  serde::Dec d(resp.value().data(), resp.value().size());
-  d.num<uint64_t>();  // view version
-  const uint64_t token = d.num<uint64_t>();  // 0 = no session granted
-  const uint16_t npools = d.num<uint16_t>();
-  std::vector<PoolRef> pools(npools);
-  for (uint16_t i = 0; i < npools; ++i) {
-    pools[i].pool_id = d.str();
-    pools[i].base = resolve_pool_base(pools[i].pool_id, &pools[i].access,
-                                      &pools[i].same_device);
-  }
+  wire::BatchPlacements pl;
+  BB_RETURN_IF_ERROR(
+      wire::decode_put_start2_response(resp.value(), items.size(), pl));
+  const uint64_t token = pl.token;  // 0 = no session granted
+  const auto pools = resolve_pools(pl.pools);
 
   std::vector<int32_t> statuses(items.size(), 0);
-  std::vector<gpu::CopyDesc> fused;
-  std::vector<gpu::PutDesc> fused_hash;
-  std::vector<uint32_t> fused_hash_idx;
-  std::vector<std::pair<PoolId, uint64_t>> fused_hash_loc;  // placement cache
-  std::vector<uint32_t> committed_idx;
-  std::vector<std::pair<ShardPlacement, const void*>> staged_put_work;
-  std::vector<uint32_t> staged_put_idx;
-  int si = 0;
+  Router<true> rt(*this, fused_copy_, /*defer=*/true);
+  std::vector<std::pair<PoolId, uint64_t>> hashed_loc;  // placement cache
 
-  for (size_t i = 0; i < items.size() && d.ok(); ++i) {
-    if (d.num<uint8_t>() != 0) {  // placement error
-      statuses[i] = d.num<int32_t>();
+  for (size_t i = 0; i < items.size(); ++i) {
+    const wire::ItemPlaces& ip = pl.items[i];
+    if (ip.status != 0) {  // placement error
+      statuses[i] = ip.status;
       continue;
     }
-    const uint8_t ncopies = d.num<uint8_t>();
-    bool ok = true;
-    bool hashed_in_fuse = false;
+    const wire::Place* places = pl.places_of(ip);
+    const uint8_t* isrc = static_cast<const uint8_t*>(items[i].ptr);
     // fused copy+digest fast path: every copy base-resolvable + aligned
     // (one desc per copy, digests identical across replicas)
-    const uint8_t* isrc = static_cast<const uint8_t*>(items[i].ptr);
-    bool all_fusable = fused_copy_ && cfg.checksum && ncopies == dpi &&
-                       (reinterpret_cast<uintptr_t>(isrc) & 15) == 0;
-    std::pair<uint16_t, uint64_t> places[8];
-    if (ncopies <= 8) {
-      // decode ALL copies first (the wire cursor must always advance),
-      // then decide fused vs general
-      for (uint8_t c = 0; c < ncopies; ++c)
-        places[c] = {d.num<uint16_t>(), d.num<uint64_t>()};
-      for (uint8_t c = 0; c < ncopies && all_fusable; ++c) {
-        PoolRef* pr = places[c].first < npools ? &pools[places[c].first]
-                                               : nullptr;
-        if (!pr || !pr->base ||
-            (reinterpret_cast<uintptr_t>(pr->base + places[c].second) & 15))
-          all_fusable = false;
+    bool all_fusable =
+        fused_copy_ && cfg.checksum && ip.ncopies == dpi && aligned16(isrc);
+    for (uint8_t c = 0; c < ip.ncopies && all_fusable; ++c)
+      all_fusable =
+          places[c].pool_idx < pools.size() && pools[places[c].pool_idx].base &&
+          aligned16(pools[places[c].pool_idx].base + places[c].offset);
+    if (all_fusable) {
+      for (uint8_t c = 0; c < ip.ncopies; ++c) {
+        const PoolRef& pr = pools[places[c].pool_idx];
+        rt.hashed.push_back({isrc, pr.base + places[c].offset, items[i].size});
+        if (c == 0)  // the verified-get cache reads copy 0
+          hashed_loc.emplace_back(pr.pool_id, places[c].offset);
       }
-      if (all_fusable) {
-        for (uint8_t c = 0; c < ncopies; ++c) {
-          PoolRef& pr = pools[places[c].first];
-          fused_hash.push_back(
-              {isrc, pr.base + places[c].second, items[i].size});
-          if (c == 0)  // the verified-get cache reads copy 0
-            fused_hash_loc.emplace_back(pr.pool_id, places[c].second);
-        }
-        hashed_in_fuse = true;
-      } else {
-        // fall through: route the already-decoded copies the general way
-        for (uint8_t c = 0; c < ncopies && ok; ++c) {
-          auto [pi, off] = places[c];
-          if (pi >= npools) { ok = false; break; }
-          PoolRef& pr = pools[pi];
-          if (pr.base) {
-            if (fused_copy_)
-              fused.push_back({isrc, pr.base + off, items[i].size});
-            else {
-              hipError_t e = hipMemcpyAsync(pr.base + off, isrc,
-                                            items[i].size,
-                                            hipMemcpyDeviceToDevice,
-                                            streams_[si % kStreams]);
-              if (e != hipSuccess) {
-                (void)hipGetLastError();
-                ok = false;
-                break;
-              }
-              ++si;
-            }
-          } else {
-            ShardPlacement sp;
-            sp.pool_id = pr.pool_id;
-            sp.offset = off;
-            sp.length = items[i].size;
-            sp.access = pr.access;
-            staged_put_work.emplace_back(std::move(sp), isrc);
-            staged_put_idx.push_back(static_cast<uint32_t>(i));
-          }
-        }
-      }
-    } else
-    for (uint8_t c = 0; c < ncopies; ++c) {
-      const uint16_t pi = d.num<uint16_t>();
-      const uint64_t off = d.num<uint64_t>();
-      if (pi >= npools) { ok = false; break; }
-      PoolRef& pr = pools[pi];
-      const uint8_t* src = static_cast<const uint8_t*>(items[i].ptr);
-      if (pr.base) {
-        uint8_t* dst = pr.base + off;
-        if (fused_copy_) {
-          fused.push_back({src, dst, items[i].size});
-        } else {
-          hipError_t e = hipMemcpyAsync(dst, src, items[i].size,
-                                        hipMemcpyDeviceToDevice,
-                                        streams_[si % kStreams]);
-          if (e != hipSuccess) { ok = false; break; }
-          ++si;
-        }
-      } else {
-        ShardPlacement sp;
-        sp.pool_id = pr.pool_id;
-        sp.offset = off;
-        sp.length = items[i].size;
-        sp.access = pr.access;
-        staged_put_work.emplace_back(std::move(sp), src);
-        staged_put_idx.push_back(static_cast<uint32_t>(i));
-      }
-    }
-    if (!ok) {
-      statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
+      rt.hashed_idx.push_back(static_cast<uint32_t>(i));
       continue;
     }
-    if (hashed_in_fuse) fused_hash_idx.push_back(static_cast<uint32_t>(i));
-    else committed_idx.push_back(static_cast<uint32_t>(i));
+    // general route; a copy naming a pool outside the table fails the item
+    bool ok = true;
+    for (uint8_t c = 0; c < ip.ncopies && ok; ++c)
+      ok = places[c].pool_idx < pools.size() &&
+           rt.add(isrc, pools[places[c].pool_idx], places[c].offset,
+                  items[i].size, static_cast<uint32_t>(i)).ok();
+    if (ok) rt.plain_idx.push_back(static_cast<uint32_t>(i));
+    else statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
-  if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 response"};
   // unmappable pools (direct-IO NVMe tier, TCP-only remotes): fan the staged
   // writes out on a side thread so the disk overlaps the kernel launches and
   // digest passes below
   std::future<Result<void>> staged_fut;
-  if (!staged_put_work.empty())
+  if (!rt.staged.empty())
     staged_fut = std::async(std::launch::async, [&] {
       (void)hipSetDevice(device_);
-      return staged_write_many(staged_put_work);
+      return staged_write_many(rt.staged);
     });
-
-  if (!fused.empty()) {
-    auto r = gpu::batched_copy(fused.data(), static_cast<uint32_t>(fused.size()),
-                               streams_[0]);
-    if (!r.ok()) return r.error();
-  }
-  std::vector<uint64_t> digests(committed_idx.size(), 0);
-  if (cfg.checksum && !committed_idx.empty()) {
-    std::vector<const void*> ptrs;
-    std::vector<uint64_t> sizes;
-    for (auto i : committed_idx) {
-      ptrs.push_back(items[i].ptr);
-      sizes.push_back(items[i].size);
-    }
-    auto r = gpu::checksum_batch(ptrs.data(), sizes.data(),
-                                 static_cast<uint32_t>(ptrs.size()),
-                                 digests.data(), device_, streams_[1]);
-    if (!r.ok()) return r.error();
-  }
-  std::vector<uint64_t> fused_digests(fused_hash.size(), 0);
-  if (!fused_hash.empty()) {
-    auto r = gpu::fused_put(fused_hash.data(),
-                            static_cast<uint32_t>(fused_hash.size()),
-                            fused_digests.data(), streams_[2]);
-    if (!r.ok()) return r.error();  // synchronizes stream 2 itself
-  }
-  // only streams that actually carried work need a sync: the rotating SDMA
-  // streams (si of them) and stream 0 (fused copy list); checksum_batch and
-  // fused_put synchronize their own streams internally
-  if (!fused.empty()) BB_HIP(hipStreamSynchronize(streams_[0]));
-  for (int j = 0; j < std::min(si, kStreams); ++j)
-    BB_HIP(hipStreamSynchronize(streams_[j]));
+  BB_RETURN_IF_ERROR(rt.launch_put(items, cfg.checksum));
   if (staged_fut.valid()) {
     auto r = staged_fut.get();
     if (!r.ok())  // failed staged items must not commit (cancelled below)
-      for (auto i : staged_put_idx)
+      for (auto i : rt.staged_idx)
         statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
+  const bool all_hashed = rt.hashed_idx.size() == items.size();
 
   // commit: token path (8 B + digests, no key strings) when the whole batch
-  // rode the fused single-copy path; key-based BATCH_PUT_COMPLETE otherwise
-  // (or if the token went stale — concurrent placement change)
-  bool committed_by_token = false;
-  if (token != 0 && fused_hash_idx.size() == items.size()) {
-    serde::Enc e2;
-    e2.num<uint64_t>(token);
-    e2.num<uint8_t>(establish ? 0 : 1);  // one-shot: release after commit
-    e2.num<uint32_t>(static_cast<uint32_t>(fused_hash_idx.size()));
-    for (size_t j = 0; j < fused_hash_idx.size(); ++j)
-      e2.num<uint64_t>(fused_digests[j * dpi]);
-    auto r2 = c_.meta_call_raw(M::BATCH_COMMIT_TOKEN, e2.buf);
-    committed_by_token = r2.ok();
-  }
-  if (!committed_by_token) {
-    PutCompleteListMsg completes;
-    for (size_t j = 0; j < committed_idx.size(); ++j) {
-      if (statuses[committed_idx[j]] != 0) continue;  // staged write failed
-      completes.reqs.push_back(
-          PutCompleteRequest{items[committed_idx[j]].key, digests[j], {}});
-    }
-    for (size_t j = 0; j < fused_hash_idx.size(); ++j)
-      completes.reqs.push_back(PutCompleteRequest{
-          items[fused_hash_idx[j]].key, fused_digests[j * dpi], {}});
-    if (!completes.reqs.empty()) {
-      auto r = c_.meta_call<PutCompleteListMsg, StatusListMsg>(
-          M::BATCH_PUT_COMPLETE, completes);
-      if (!r.ok()) return r.error();
-    }
-  }
-  if (placement_cache_on_ && !fused_hash_idx.empty()) {
+  // rode the fused single-copy path (one-shot tokens are released by the
+  // commit); key-based BATCH_PUT_COMPLETE otherwise, or if the token went
+  // stale (concurrent placement change)
+  const bool committed_by_token =
+      token != 0 && all_hashed &&
+      c_.commit_by_token(token, /*release=*/!establish,
+                         rt.hashed_digests.data(), items.size(), dpi).ok();
+  if (!committed_by_token)
+    BB_RETURN_IF_ERROR(complete_puts(items, rt, dpi, nullptr, statuses,
+                                     /*apply_statuses=*/false));
+  if (placement_cache_on_ && !rt.hashed_idx.empty()) {
     // remember our own single-copy placements + digests for RPC-free
     // verified gets (see set_placement_cache)
     std::lock_guard<std::mutex> g(cache_mu_);
-    for (size_t j = 0; j < fused_hash_idx.size(); ++j) {
-      const auto& it = items[fused_hash_idx[j]];
-      if (fused_digests[j * dpi] == 0) continue;  // 0 marks "no digest"
-      CachedPlacement np{fused_hash_loc[j].first, fused_hash_loc[j].second,
-                         it.size, fused_digests[j * dpi]};
+    for (size_t j = 0; j < rt.hashed_idx.size(); ++j) {
+      const auto& it = items[rt.hashed_idx[j]];
+      if (rt.hashed_digests[j * dpi] == 0) continue;  // 0 marks "no digest"
+      CachedPlacement np{hashed_loc[j].first, hashed_loc[j].second,
+                         it.size, rt.hashed_digests[j * dpi]};
       auto [cit, inserted] = placement_cache_.try_emplace(it.key, np);
       if (!inserted) {
         // overwrite with a MOVED placement (e.g. re-placed after a worker
@@ -769,17 +791,16 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
     }
     // establish the batch session when the server granted a token AND every
     // item rode the fused single-copy path (so desc j == item j)
-    if (sess && establish && token != 0 &&
-        fused_hash_idx.size() == items.size()) {
+    if (sess && establish && token != 0 && all_hashed) {
       bool all_cached = true;
-      sess->descs = fused_hash;
+      sess->descs = rt.hashed;
       sess->descs_per_item = dpi;
       sess->plan.reset();  // descs changed: a kept plan would replay stale
       sess->plan_failed = false;
       sess->entries.clear();
       sess->entries.reserve(items.size());
       for (size_t j = 0; j < items.size() && all_cached; ++j) {
-        auto cit = placement_cache_.find(items[fused_hash_idx[j]].key);
+        auto cit = placement_cache_.find(items[rt.hashed_idx[j]].key);
         if (cit == placement_cache_.end()) all_cached = false;
         else sess->entries.push_back(&cit->second);
       }
@@ -794,12 +815,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
       }
     }
   }
-  std::vector<std::string> cancels;
-  for (size_t i = 0; i < items.size(); ++i)
-    if (statuses[i] == static_cast<int32_t>(ErrorCode::TRANSFER_FAILED))
-      cancels.push_back(items[i].key);
-  if (!cancels.empty())
-    c_.meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{cancels}));
+  cancel_failed(items, statuses);
   return statuses;
 }
 
@@ -822,10 +838,6 @@ void GpuClient::clear_placement_cache() {
   std::lock_guard<std::mutex> g(cache_mu_);
   placement_cache_.clear();
   ++cache_epoch_;
-}
-
-uint8_t* GpuClient::device_pool_base(const PoolId& id) {
-  return resolve_pool_base(id, nullptr, nullptr);
 }
 
 // Session fast path for gets: descs and want-digest slots were resolved on a
@@ -917,7 +929,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
   std::vector<CachedPlacement*> hit_entries;
   for (size_t li = 0; li < lookups.size(); ++li) {
     auto& [i, cp] = lookups[li];
-    uint8_t* base = device_pool_base(cp.pool_id);
+    uint8_t* base = resolve_pool_base(cp.pool_id);
     const auto du = reinterpret_cast<uintptr_t>(items[i].ptr);
     if (base &&
         ((du | reinterpret_cast<uintptr_t>(base + cp.offset)) & 15) == 0) {
@@ -977,140 +989,66 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
 Result<std::vector<int32_t>> GpuClient::batch_get_device_rpc(
     const std::vector<DevGetItem>& items, bool verify) {
   BB_TRACE_SCOPE("bb::batch_get");
-  serde::Enc req;
-  req.num<uint32_t>(static_cast<uint32_t>(items.size()));
-  for (auto& it : items) req.str(it.key);
-  auto resp = c_.meta_call_raw(rpc::methods::BATCH_GET_WORKERS2, req.buf);
+  auto resp = c_.meta_call_raw(M::BATCH_GET_WORKERS2,
+                               wire::encode_get_workers2_request(items));
   if (!resp.ok()) return resp.error();
-
-  serde::Dec d(resp.value().data(), resp.value().size());
-  const uint16_t npools = d.num<uint16_t>();
-  std::vector<PoolRef> pools(npools);
-  for (uint16_t i = 0; i < npools; ++i) {
-    pools[i].pool_id = d.str();
-    pools[i].base = resolve_pool_base(pools[i].pool_id, &pools[i].access,
-                                      &pools[i].same_device);
-  }
+  wire::BatchPlacements pl;
+  BB_RETURN_IF_ERROR(
+      wire::decode_get_workers2_response(resp.value(), items.size(), pl));
+  const auto pools = resolve_pools(pl.pools);
 
   std::vector<int32_t> statuses(items.size(), 0);
-  std::vector<gpu::CopyDesc> fused;
-  std::vector<std::pair<ShardPlacement, void*>> staged_work;
-  std::vector<uint32_t> staged_idx;
-  // verify mode: the gather rides the copy+digest kernel, so verification
-  // costs no extra read of the data
-  std::vector<gpu::PutDesc> fused_v;
-  std::vector<uint32_t> fused_v_idx;
-  std::vector<uint32_t> fetched;
-  std::vector<uint64_t> want_checksum(items.size(), 0);
-  std::vector<uint64_t> got_size(items.size(), 0);
-  int si = 0;
-
-  for (size_t i = 0; i < items.size() && d.ok(); ++i) {
-    if (d.num<uint8_t>() != 0) {
-      statuses[i] = d.num<int32_t>();
+  Router<false> rt(*this, fused_copy_, /*defer=*/true);
+  for (size_t i = 0; i < items.size(); ++i) {
+    const wire::ItemPlaces& ip = pl.items[i];
+    if (ip.status != 0) {
+      statuses[i] = ip.status;
       continue;
     }
-    const uint64_t size = d.num<uint64_t>();
-    want_checksum[i] = d.num<uint64_t>();
-    got_size[i] = size;
-    const uint8_t ncopies = d.num<uint8_t>();
-    if (size > items[i].capacity) {
+    if (ip.size > items[i].capacity) {
       statuses[i] = static_cast<int32_t>(ErrorCode::SIZE_MISMATCH);
-      for (uint8_t c = 0; c < ncopies; ++c) { d.num<uint16_t>(); d.num<uint64_t>(); }
       continue;
     }
+    uint8_t* dst = static_cast<uint8_t*>(items[i].ptr);
     bool done = false;
     Error last{ErrorCode::NO_PLACEMENT, "no copies"};
-    for (uint8_t c = 0; c < ncopies; ++c) {
-      const uint16_t pi = d.num<uint16_t>();
-      const uint64_t off = d.num<uint64_t>();
-      if (done || pi >= npools) continue;
-      PoolRef& pr = pools[pi];
-      uint8_t* dst = static_cast<uint8_t*>(items[i].ptr);
-      if (pr.base) {
-        const auto du = reinterpret_cast<uintptr_t>(dst);
-        if (fused_copy_ && verify && want_checksum[i] != 0 &&
-            ((du | reinterpret_cast<uintptr_t>(pr.base + off)) & 15) == 0) {
-          fused_v.push_back({pr.base + off, dst, size});
-          fused_v_idx.push_back(static_cast<uint32_t>(i));
-          done = true;
-        } else if (fused_copy_) {
-          fused.push_back({pr.base + off, dst, size});
-          done = true;
-        } else {
-          hipError_t e = hipMemcpyAsync(dst, pr.base + off, size,
-                                        hipMemcpyDeviceToDevice,
-                                        streams_[si % kStreams]);
-          if (e == hipSuccess) { done = true; ++si; }
-          else last = Error{ErrorCode::HIP_ERROR, hipGetErrorString(e)};
-        }
+    for (uint8_t c = 0; c < ip.ncopies && !done; ++c) {
+      const wire::Place& p = pl.places_of(ip)[c];
+      if (p.pool_idx >= pools.size()) continue;  // unknown pool: skip copy
+      const PoolRef& pr = pools[p.pool_idx];
+      // verify mode: the gather rides the copy+digest kernel, so
+      // verification costs no extra read of the data
+      if (pr.base && fused_copy_ && verify && ip.checksum != 0 &&
+          aligned16(dst, pr.base + p.offset)) {
+        rt.hashed.push_back({pr.base + p.offset, dst, ip.size});
+        rt.hashed_idx.push_back(static_cast<uint32_t>(i));
+        done = true;
+        continue;
+      }
+      // (a staged copy counts as fetched: completion is checked after the
+      // fan-out below)
+      auto r = rt.add(dst, pr, p.offset, ip.size, static_cast<uint32_t>(i));
+      if (r.ok()) {
+        rt.plain_idx.push_back(static_cast<uint32_t>(i));
+        done = true;
       } else {
-        ShardPlacement sp;
-        sp.pool_id = pr.pool_id;
-        sp.offset = off;
-        sp.length = size;
-        sp.access = pr.access;
-        staged_work.emplace_back(std::move(sp), dst);
-        staged_idx.push_back(static_cast<uint32_t>(i));
-        done = true;  // completion checked after the fan-out below
+        last = r.error();
       }
     }
-    if (done) fetched.push_back(static_cast<uint32_t>(i));
-    else statuses[i] = static_cast<int32_t>(last.code);
+    if (!done) statuses[i] = static_cast<int32_t>(last.code);
   }
-  if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 response"};
-  if (!staged_work.empty()) {
-    auto r = staged_read_many(staged_work);
-    if (!r.ok()) {
+  if (!rt.staged.empty()) {
+    auto r = staged_read_many(rt.staged);
+    if (!r.ok())
       // mark the whole staged group failed (partial data is not returned)
-      for (auto i : staged_idx)
-        statuses[i] = static_cast<int32_t>(r.code());
-    }
+      for (auto i : rt.staged_idx) statuses[i] = static_cast<int32_t>(r.code());
   }
-
-  if (!fused.empty()) {
-    auto r = gpu::batched_copy(fused.data(), static_cast<uint32_t>(fused.size()),
-                               streams_[0]);
-    if (!r.ok()) return r.error();
-  }
-  std::vector<uint64_t> fused_v_digests(fused_v.size(), 0);
-  if (!fused_v.empty()) {
-    auto r = gpu::fused_put(fused_v.data(), static_cast<uint32_t>(fused_v.size()),
-                            fused_v_digests.data(), streams_[2]);
-    if (!r.ok()) return r.error();  // synchronizes stream 2 itself
-    for (size_t j = 0; j < fused_v_idx.size(); ++j)
-      if (fused_v_digests[j] != want_checksum[fused_v_idx[j]])
-        statuses[fused_v_idx[j]] =
-            static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
-  }
-  if (!fused.empty()) BB_HIP(hipStreamSynchronize(streams_[0]));
-  for (int j = 0; j < std::min(si, kStreams); ++j)
-    BB_HIP(hipStreamSynchronize(streams_[j]));
-
-  if (verify) {
-    // items whose gather rode the copy+digest kernel are already verified
-    std::vector<bool> pre_verified(items.size(), false);
-    for (auto i : fused_v_idx) pre_verified[i] = true;
-    std::vector<const void*> ptrs;
-    std::vector<uint64_t> sizes;
-    std::vector<uint32_t> idxs;
-    for (auto i : fetched) {
-      if (pre_verified[i]) continue;
-      ptrs.push_back(items[i].ptr);
-      sizes.push_back(got_size[i]);
-      idxs.push_back(i);
-    }
-    if (!ptrs.empty()) {
-      std::vector<uint64_t> got(ptrs.size());
-      auto r = gpu::checksum_batch(ptrs.data(), sizes.data(),
-                                   static_cast<uint32_t>(ptrs.size()), got.data(),
-                                   device_, streams_[0]);
-      if (!r.ok()) return r.error();
-      for (size_t j = 0; j < idxs.size(); ++j)
-        if (want_checksum[idxs[j]] != 0 && got[j] != want_checksum[idxs[j]])
-          statuses[idxs[j]] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
-    }
-  }
+  BB_RETURN_IF_ERROR(rt.finish_get(
+      items, verify,
+      [&](uint32_t i) {
+        return std::make_pair(pl.items[i].size, pl.items[i].checksum);
+      },
+      statuses));
   return statuses;
 }
 
@@ -1119,24 +1057,11 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_rpc(
 Result<std::vector<int32_t>> GpuClient::batch_put_device(
     const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
     BatchPutSession* sess) {
-  const uint64_t gen = c_.reconnect_generation();
-  auto st = batch_put_device_once(items, cfg, sess);
-  if (!st.ok() || c_.reconnect_generation() == gen) return st;
   // keystone failover mid-batch: the new leader never saw this batch's
-  // PENDING state — redo the failover-shaped failures once
-  std::vector<DevPutItem> redo;
-  std::vector<size_t> redo_idx;
-  for (size_t i = 0; i < items.size(); ++i)
-    if (Client::failover_retriable(st.value()[i])) {
-      redo.push_back(items[i]);
-      redo_idx.push_back(i);
-    }
-  if (redo.empty()) return st;
-  auto st2 = batch_put_device_once(redo, cfg, nullptr);
-  if (!st2.ok()) return st;
-  for (size_t j = 0; j < redo_idx.size(); ++j)
-    st.value()[redo_idx[j]] = st2.value()[j];
-  return st;
+  // PENDING state — the failover-shaped failures are redone once
+  return c_.redo_after_failover(items, [&](const auto& its, bool first) {
+    return batch_put_device_once(its, cfg, first ? sess : nullptr);
+  });
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
@@ -1156,11 +1081,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
   if (!start.ok()) return start.error();
 
   std::vector<int32_t> statuses(items.size(), 0);
-  std::vector<gpu::CopyDesc> fused;        // copy-only kernel batch
-  std::vector<gpu::PutDesc> fused_hash;    // copy+digest kernel batch
-  std::vector<uint32_t> fused_hash_idx;
-  std::vector<uint32_t> committed_idx;     // transferred, digest via source hash
-  int si = 0;
+  Router<true> rt(*this, fused_copy_, /*defer=*/false);
 
   for (size_t i = 0; i < items.size(); ++i) {
     auto& placed = start->items[i];
@@ -1168,93 +1089,40 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
       statuses[i] = placed.status;
       continue;
     }
-    // fast path: single local same-device shard + digest wanted → ONE fused
+    // fast path: single device-visible shard + digest wanted → ONE fused
     // copy+hash kernel reads the object once
     if (fused_copy_ && cfg.checksum && placed.copies.size() == 1 &&
         placed.copies[0].shards.size() == 1) {
-      const auto& sh = placed.copies[0].shards[0];
-      auto res = resolve_device_ptr(sh);
-      const auto src_u = reinterpret_cast<uintptr_t>(items[i].ptr);
-      if (res.ptr &&
-          ((src_u | reinterpret_cast<uintptr_t>(res.ptr)) & 15) == 0) {
-        fused_hash.push_back({items[i].ptr, res.ptr, items[i].size});
-        fused_hash_idx.push_back(static_cast<uint32_t>(i));
+      uint8_t* dst = resolve_device_ptr(placed.copies[0].shards[0]);
+      if (dst && aligned16(items[i].ptr, dst)) {
+        rt.hashed.push_back({items[i].ptr, dst, items[i].size});
+        rt.hashed_idx.push_back(static_cast<uint32_t>(i));
         continue;
       }
     }
     bool ok = true;
-    for (const auto& copy : placed.copies) {
-      uint64_t off = 0;
-      for (const auto& s : copy.shards) {
-        const uint8_t* src = static_cast<const uint8_t*>(items[i].ptr) + off;
-        if (auto res = resolve_device_ptr(s); res.ptr) {
-          if (fused_copy_) {
-            fused.push_back({src, res.ptr, s.length});
-          } else {
-            hipError_t e = hipMemcpyAsync(res.ptr, src, s.length,
-                                          hipMemcpyDeviceToDevice,
-                                          streams_[si % kStreams]);
-            if (e != hipSuccess) {
-              ok = false;
-              break;
-            }
-            ++si;
-          }
-        } else {
-          auto r = staged_write(s, src);
-          if (!r.ok()) {
-            ok = false;
-            break;
-          }
-        }
-        off += s.length;
-      }
-      if (!ok) break;
-    }
-    if (ok) committed_idx.push_back(static_cast<uint32_t>(i));
+    for (const auto& copy : placed.copies)
+      if (!(ok = rt.add_copy(static_cast<const uint8_t*>(items[i].ptr), copy,
+                             static_cast<uint32_t>(i)).ok()))
+        break;
+    if (ok) rt.plain_idx.push_back(static_cast<uint32_t>(i));
     else statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
-
-  if (!fused.empty()) {
-    auto r = gpu::batched_copy(fused.data(), static_cast<uint32_t>(fused.size()),
-                               streams_[0]);
-    if (!r.ok()) return r.error();
-  }
-
-  // digest launch for the non-fused group (hashes the SOURCE buffers, so it
-  // overlaps the cross-device SDMA copies on other streams)
-  std::vector<uint64_t> digests(committed_idx.size(), 0);
-  if (cfg.checksum && !committed_idx.empty()) {
-    std::vector<const void*> ptrs;
-    std::vector<uint64_t> sizes;
-    for (auto i : committed_idx) {
-      ptrs.push_back(items[i].ptr);
-      sizes.push_back(items[i].size);
-    }
-    auto r = gpu::checksum_batch(ptrs.data(), sizes.data(),
-                                 static_cast<uint32_t>(ptrs.size()),
-                                 digests.data(), device_, streams_[1]);
-    if (!r.ok()) return r.error();
-  }
-  // fused copy+digest group (blocks on stream 2)
-  std::vector<uint64_t> fused_digests(fused_hash.size(), 0);
-  if (!fused_hash.empty()) {
-    auto r = gpu::fused_put(fused_hash.data(),
-                            static_cast<uint32_t>(fused_hash.size()),
-                            fused_digests.data(), streams_[2]);
-    if (!r.ok()) return r.error();
-  }
-  for (auto& st : streams_) BB_HIP(hipStreamSynchronize(st));
+  BB_RETURN_IF_ERROR(rt.launch_put(items, cfg.checksum));
 
   // per-shard digests for striped copies (one batched launch hashes every
   // source slice) — recorded server-side so the scrubber can verify each
   // striped shard independently
   std::map<uint32_t, std::vector<std::vector<uint64_t>>> shard_digests;
   if (cfg.checksum) {
-    std::vector<const void*> sptrs;
-    std::vector<uint64_t> ssizes;
-    std::vector<std::tuple<uint32_t, uint32_t, uint32_t>> slots;  // item,copy,shard
-    for (auto i : committed_idx) {
+    struct Slot {
+      uint32_t item, copy, shard;
+      const void* ptr;
+      uint64_t size;
+    };
+    std::vector<Slot> slots;
+    std::vector<uint32_t> slot_idx;
+    for (auto i : rt.plain_idx) {
       const auto& copies = start->items[i].copies;
       bool striped = false;
       for (const auto& c : copies)
@@ -1266,74 +1134,34 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
         out[c].resize(copies[c].shards.size(), 0);
         uint64_t off = 0;
         for (uint32_t s2 = 0; s2 < copies[c].shards.size(); ++s2) {
-          sptrs.push_back(static_cast<const uint8_t*>(items[i].ptr) + off);
-          ssizes.push_back(copies[c].shards[s2].length);
-          slots.emplace_back(i, c, s2);
+          slot_idx.push_back(static_cast<uint32_t>(slots.size()));
+          slots.push_back({i, c, s2,
+                           static_cast<const uint8_t*>(items[i].ptr) + off,
+                           copies[c].shards[s2].length});
           off += copies[c].shards[s2].length;
         }
       }
     }
-    if (!sptrs.empty()) {
-      std::vector<uint64_t> got(sptrs.size(), 0);
-      auto r = gpu::checksum_batch(sptrs.data(), ssizes.data(),
-                                   static_cast<uint32_t>(sptrs.size()),
-                                   got.data(), device_, streams_[1]);
-      if (!r.ok()) return r.error();
-      for (size_t k = 0; k < slots.size(); ++k) {
-        auto [i, c, s2] = slots[k];
-        shard_digests[i][c][s2] = got[k];
-      }
-    }
+    auto got = digest_items(
+        slot_idx, [&](uint32_t k) { return slots[k].ptr; },
+        [&](uint32_t k) { return slots[k].size; }, streams_[1]);
+    if (!got.ok()) return got.error();
+    for (size_t k = 0; k < slots.size(); ++k)
+      shard_digests[slots[k].item][slots[k].copy][slots[k].shard] =
+          got.value()[k];
   }
 
-  PutCompleteListMsg completes;
-  std::vector<uint32_t> complete_order;
-  for (size_t j = 0; j < committed_idx.size(); ++j) {
-    PutCompleteRequest pc{items[committed_idx[j]].key, digests[j], {}};
-    auto it = shard_digests.find(committed_idx[j]);
-    if (it != shard_digests.end()) pc.shard_digests = std::move(it->second);
-    completes.reqs.push_back(std::move(pc));
-    complete_order.push_back(committed_idx[j]);
-  }
-  for (size_t j = 0; j < fused_hash_idx.size(); ++j) {
-    completes.reqs.push_back(
-        PutCompleteRequest{items[fused_hash_idx[j]].key, fused_digests[j], {}});
-    complete_order.push_back(fused_hash_idx[j]);
-  }
-  if (!completes.reqs.empty()) {
-    auto r = c_.meta_call<PutCompleteListMsg, StatusListMsg>(
-        M::BATCH_PUT_COMPLETE, completes);
-    if (!r.ok()) return r.error();
-    for (size_t j = 0; j < complete_order.size() && j < r->statuses.size(); ++j)
-      if (r->statuses[j] != 0) statuses[complete_order[j]] = r->statuses[j];
-  }
-  std::vector<std::string> cancels;
-  for (size_t i = 0; i < items.size(); ++i)
-    if (statuses[i] == static_cast<int32_t>(ErrorCode::TRANSFER_FAILED))
-      cancels.push_back(items[i].key);
-  if (!cancels.empty())
-    c_.meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{cancels}));
+  BB_RETURN_IF_ERROR(complete_puts(items, rt, 1, &shard_digests, statuses,
+                                   /*apply_statuses=*/true));
+  cancel_failed(items, statuses);
   return statuses;
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_get_device(
     const std::vector<DevGetItem>& items, bool verify, BatchGetSession* sess) {
-  const uint64_t gen = c_.reconnect_generation();
-  auto st = batch_get_device_once(items, verify, sess);
-  if (!st.ok() || c_.reconnect_generation() == gen) return st;
-  std::vector<DevGetItem> redo;
-  std::vector<size_t> redo_idx;
-  for (size_t i = 0; i < items.size(); ++i)
-    if (Client::failover_retriable(st.value()[i])) {
-      redo.push_back(items[i]);
-      redo_idx.push_back(i);
-    }
-  if (redo.empty()) return st;
-  auto st2 = batch_get_device_once(redo, verify, nullptr);
-  if (!st2.ok()) return st;
-  for (size_t j = 0; j < redo_idx.size(); ++j)
-    st.value()[redo_idx[j]] = st2.value()[j];
-  return st;
+  return c_.redo_after_failover(items, [&](const auto& its, bool first) {
+    return batch_get_device_once(its, verify, first ? sess : nullptr);
+  });
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
@@ -1360,9 +1188,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
   if (!meta.ok()) return meta.error();
 
   std::vector<int32_t> statuses(items.size(), 0);
-  std::vector<gpu::CopyDesc> fused;
-  std::vector<uint32_t> fetched;
-  int si = 0;
+  Router<false> rt(*this, fused_copy_, /*defer=*/false);
 
   for (size_t i = 0; i < items.size(); ++i) {
     auto& item = meta->items[i];
@@ -1375,64 +1201,20 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
       continue;
     }
     bool ok = false;
-    for (const auto& copy : item.info.copies) {
-      ok = true;
-      uint64_t off = 0;
-      for (const auto& s : copy.shards) {
-        uint8_t* dst = static_cast<uint8_t*>(items[i].ptr) + off;
-        if (auto res = resolve_device_ptr(s); res.ptr) {
-          if (fused_copy_) {
-            fused.push_back({res.ptr, dst, s.length});
-          } else {
-            hipError_t e = hipMemcpyAsync(dst, res.ptr, s.length,
-                                          hipMemcpyDeviceToDevice,
-                                          streams_[si % kStreams]);
-            if (e != hipSuccess) {
-              ok = false;
-              break;
-            }
-            ++si;
-          }
-        } else {
-          auto r = staged_read(s, dst);
-          if (!r.ok()) {
-            ok = false;
-            break;
-          }
-        }
-        off += s.length;
-      }
-      if (ok) break;  // first healthy copy wins
-    }
-    if (ok) fetched.push_back(static_cast<uint32_t>(i));
+    for (const auto& copy : item.info.copies)
+      if ((ok = rt.add_copy(static_cast<uint8_t*>(items[i].ptr), copy,
+                            static_cast<uint32_t>(i)).ok()))
+        break;  // first healthy copy wins
+    if (ok) rt.plain_idx.push_back(static_cast<uint32_t>(i));
     else statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
-
-  if (!fused.empty()) {
-    auto r = gpu::batched_copy(fused.data(), static_cast<uint32_t>(fused.size()),
-                               streams_[0]);
-    if (!r.ok()) return r.error();
-  }
-  for (auto& st : streams_) BB_HIP(hipStreamSynchronize(st));
-
-  if (verify && !fetched.empty()) {
-    std::vector<const void*> ptrs;
-    std::vector<uint64_t> sizes;
-    std::vector<uint64_t> want;
-    for (auto i : fetched) {
-      ptrs.push_back(items[i].ptr);
-      sizes.push_back(meta->items[i].info.size);
-      want.push_back(meta->items[i].info.checksum);
-    }
-    std::vector<uint64_t> got(ptrs.size());
-    auto r = gpu::checksum_batch(ptrs.data(), sizes.data(),
-                                 static_cast<uint32_t>(ptrs.size()), got.data(),
-                                 device_, streams_[0]);
-    if (!r.ok()) return r.error();
-    for (size_t j = 0; j < fetched.size(); ++j)
-      if (want[j] != 0 && got[j] != want[j])
-        statuses[fetched[j]] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
-  }
+  BB_RETURN_IF_ERROR(rt.finish_get(
+      items, verify,
+      [&](uint32_t i) {
+        return std::make_pair(meta->items[i].info.size,
+                              meta->items[i].info.checksum);
+      },
+      statuses));
   return statuses;
 }
 
@@ -1458,8 +1240,8 @@ Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
         cached = true;
       }
     }
-    if (cached) {  // device_pool_base may RPC — not under the lock
-      if (uint8_t* base = device_pool_base(cp2.pool_id)) return base + cp2.offset;
+    if (cached) {  // resolve_pool_base may RPC — not under the lock
+      if (uint8_t* base = resolve_pool_base(cp2.pool_id)) return base + cp2.offset;
       return nullptr;
     }
     auto meta = c_.meta_call<KeyMsg, GetWorkersResponse>(M::GET_WORKERS,
@@ -1467,7 +1249,7 @@ Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
     if (!meta.ok() || meta->size != size) return nullptr;
     for (const auto& copy : meta->copies) {
       if (copy.shards.size() != 1) continue;
-      if (auto res = resolve_device_ptr(copy.shards[0]); res.ptr) return res.ptr;
+      if (uint8_t* p = resolve_device_ptr(copy.shards[0])) return p;
     }
     return nullptr;
   };

@@ -103,6 +103,31 @@ class Client {
   uint64_t reconnect_generation() const { return reconnect_gen_.load(); }
   // status looks like a lost-leader symptom (worth one redo after failover)?
   static bool failover_retriable(int32_t st);
+  // Run once(items, /*first=*/true); if the leader connection was
+  // re-established meanwhile, run the failover-shaped per-item failures once
+  // more through once(redo, false) and merge. The first answer is kept when
+  // the redo fails as a whole. (A session belongs to the first attempt only:
+  // the redo's item list is a different one.)
+  template <typename Item, typename Once>
+  auto redo_after_failover(const std::vector<Item>& items, Once&& once)
+      -> decltype(once(items, true)) {
+    const uint64_t gen = reconnect_generation();
+    auto st = once(items, true);
+    if (!st.ok() || reconnect_generation() == gen) return st;
+    std::vector<Item> redo;
+    std::vector<size_t> redo_idx;
+    for (size_t i = 0; i < items.size(); ++i)
+      if (failover_retriable(status_of(st.value()[i]))) {
+        redo.push_back(items[i]);
+        redo_idx.push_back(i);
+      }
+    if (redo.empty()) return st;
+    auto st2 = once(redo, false);
+    if (!st2.ok()) return st;
+    for (size_t j = 0; j < redo_idx.size(); ++j)
+      st.value()[redo_idx[j]] = std::move(st2.value()[j]);
+    return st;
+  }
   // steps served by the host session fast path (tests/bench introspection)
   uint64_t host_session_steps() const { return host_session_steps_.load(); }
 
@@ -147,6 +172,23 @@ class Client {
   // own cache-invalidation pattern, types.h:394-405).
   Result<AccessInfo> pool_access(const PoolId& id);
   void refresh_pool_cache_locked();
+
+  static int32_t status_of(int32_t st) { return st; }
+  static int32_t status_of(const std::pair<int32_t, std::string>& r) {
+    return r.first;
+  }
+  // ---- put epilogues shared by the host and GPU paths (v1 and v2) ----
+  // BATCH_COMMIT_TOKEN with digests[0], digests[stride], ... (n of them)
+  Result<void> commit_by_token(uint64_t token, bool release,
+                               const uint64_t* digests, size_t n,
+                               size_t stride = 1);
+  // BATCH_PUT_COMPLETE; reqs[j] belongs to item order[j]. Per-item commit
+  // failures land in *statuses (nullptr: the caller ignores them).
+  Result<void> complete_by_keys(const std::vector<PutCompleteRequest>& reqs,
+                                const std::vector<uint32_t>& order,
+                                std::vector<int32_t>* statuses);
+  // BATCH_PUT_CANCEL (best effort; nothing is sent for an empty list)
+  void cancel_puts(const std::vector<ObjectKey>& keys);
 
   ClientOptions opts_;
   rpc::RpcClient meta_;

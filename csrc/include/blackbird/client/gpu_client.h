@@ -14,6 +14,7 @@
 #pragma once
 
 #include <future>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -59,8 +60,9 @@ class GpuClient {
   // zero RPCs. Any server-side placement change invalidates the server
   // session (SESSION_STALE) and the client transparently falls back to the
   // full path. Sessions are bound to one item list: the item pointers are
-  // re-validated each step. Requires replace=true, replication=1,
-  // checksum=true, and the placement cache enabled.
+  // re-validated each step. Requires replace=true, checksum=true
+  // and the placement cache enabled; replicated placements are supported
+  // (one destination per copy).
   // Worker death: a re-placing put bumps the cache epoch (moved placements
   // kill sessions holding the old pool addresses). A get-session step
   // BEFORE any re-put reads the dead pool one-sidedly: across processes
@@ -148,23 +150,38 @@ class GpuClient {
   void clear_placement_cache();
 
  private:
-  struct Resolved {
-    void* ptr = nullptr;   // device-visible pointer or nullptr
-    bool same_device = false;
-  };
   // Resolve a shard to a device-visible pointer (local or IPC-mapped peer
-  // HBM); .ptr nullptr if the pool is not device-visible from this process.
-  Resolved resolve_device_ptr(const ShardPlacement& s);
+  // HBM, GPU-mapped host tier); nullptr if the pool is not device-visible
+  // from this process.
+  uint8_t* resolve_device_ptr(const ShardPlacement& s);
   Result<std::vector<int32_t>> batch_put_device_once(
       const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
       BatchPutSession* sess);
   Result<std::vector<int32_t>> batch_get_device_once(
       const std::vector<DevGetItem>& items, bool verify,
       BatchGetSession* sess);
-  // device-visible base of a pool for the v2 batch protocols (HBM local,
-  // IPC peer, or GPU-mapped host tier); nullptr → staged fallback
-  uint8_t* resolve_pool_base(const PoolId& pool_id, AccessInfo* access,
-                             bool* same_device);
+  // device-visible base of a pool (HBM local, IPC peer, or GPU-mapped host
+  // tier); nullptr → staged fallback. `hint`: access info already at hand.
+  uint8_t* resolve_pool_base(const PoolId& pool_id,
+                             AccessInfo* access = nullptr,
+                             const AccessInfo* hint = nullptr);
+  struct PoolRef;  // resolved pool-table entry of a v2 response
+  std::vector<PoolRef> resolve_pools(const std::vector<PoolId>& ids);
+  // routes a batch's transfers: fused copy list, SDMA streams or staging
+  template <bool Put>
+  struct Router;
+  template <typename PtrOf, typename SizeOf>
+  Result<std::vector<uint64_t>> digest_items(
+      const std::vector<uint32_t>& indices, PtrOf ptr_of, SizeOf size_of,
+      hipStream_t stream);
+  // put epilogues shared by the v1 and v2 paths
+  Result<void> complete_puts(
+      const std::vector<DevPutItem>& items, const Router<true>& rt,
+      size_t stride,
+      std::map<uint32_t, std::vector<std::vector<uint64_t>>>* shard_digests,
+      std::vector<int32_t>& statuses, bool apply_statuses);
+  void cancel_failed(const std::vector<DevPutItem>& items,
+                     const std::vector<int32_t>& statuses);
   Result<std::vector<int32_t>> batch_put_device_v2(
       const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
       BatchPutSession* sess);
@@ -179,8 +196,6 @@ class GpuClient {
   // the RPC leg of the v2 get (cache misses route here)
   Result<std::vector<int32_t>> batch_get_device_rpc(
       const std::vector<DevGetItem>& items, bool verify);
-  // device-visible base of a pool (local or IPC-mapped), or nullptr
-  uint8_t* device_pool_base(const PoolId& id);
   Result<void> staged_write(const ShardPlacement& s, const void* dev_src);
   Result<void> staged_write_buf(const ShardPlacement& s, const void* dev_src,
                                 void* staging, uint64_t staging_size);

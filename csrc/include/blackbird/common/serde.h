@@ -48,6 +48,10 @@ class Dec {
   }
   template <typename T>
   std::enable_if_t<std::is_arithmetic_v<T> || std::is_enum_v<T>, T> num() {
+    if constexpr (std::is_same_v<T, bool>) {
+      // any byte off the wire: copying 2..255 into a bool is undefined
+      return num<uint8_t>() != 0;
+    }
     T v{};
     raw(&v, sizeof(v));
     return v;

@@ -1,5 +1,6 @@
 #include "blackbird/keystone/keystone_rpc.h"
 
+#include "blackbird/client/batch_wire.h"
 #include "blackbird/common/log.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/net.h"
@@ -205,121 +206,58 @@ void KeystoneServer::register_handlers() {
   rpc_.register_handler(M::BATCH_PUT_START2, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
     if (!ks.is_leader())
       return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
-    serde::Dec d(b.data(), b.size());
-    uint32_t count = d.num<uint32_t>();
-    uint64_t uniform = d.num<uint64_t>();
+    auto rq = wire::decode_put_start2_request(b);
+    if (!rq.ok()) return rq.error();
+    rq->cfg.max_workers_per_copy = 1;  // v2 contract: single-shard copies
     std::vector<PutStartRequest> reqs;
-    reqs.reserve(count);
-    PlacementConfig cfg{};
-    std::vector<std::string> keys(count);
-    std::vector<uint64_t> sizes(count, uniform);
-    if (uniform == 0)
-      for (uint32_t i = 0; i < count; ++i) sizes[i] = d.num<uint64_t>();
-    for (uint32_t i = 0; i < count; ++i) keys[i] = d.str();
-    serde::get(d, cfg);
-    const uint8_t want_token = d.remaining() ? d.num<uint8_t>() : 0;
-    if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 request"};
-    cfg.max_workers_per_copy = 1;  // v2 contract: single-shard copies
-    for (uint32_t i = 0; i < count; ++i)
-      reqs.push_back({std::move(keys[i]), sizes[i], cfg});
+    reqs.reserve(rq->keys.size());
+    for (size_t i = 0; i < rq->keys.size(); ++i)
+      reqs.push_back({std::move(rq->keys[i]), rq->sizes[i], rq->cfg});
     auto resp = ks.batch_put_start(reqs);
 
-    uint64_t token = 0;
-    if (want_token) {
+    wire::BatchPlacements out;
+    out.view_version = resp.view_version;
+    if (rq->want_token) {
       bool all_ok = !resp.items.empty();
       for (auto& it : resp.items)
         if (it.status != 0) { all_ok = false; break; }
-      if (all_ok) token = ks.create_put_session(reqs);
+      if (all_ok) out.token = ks.create_put_session(reqs);
     }
-
-    serde::Enc e;
-    e.num<uint64_t>(resp.view_version);
-    e.num<uint64_t>(token);  // 0 = no session granted
-    // build the pool table
-    std::map<std::string, uint16_t> pool_idx;
-    std::vector<const std::string*> table;
+    wire::PoolTable table(out.pools);
     for (auto& it : resp.items)
-      for (auto& c : it.copies)
-        for (auto& sh : c.shards)
-          if (pool_idx.emplace(sh.pool_id, static_cast<uint16_t>(table.size())).second)
-            table.push_back(&sh.pool_id);
-    e.num<uint16_t>(static_cast<uint16_t>(table.size()));
-    for (auto* p2 : table) e.str(*p2);
-    for (auto& it : resp.items) {
-      e.num<uint8_t>(static_cast<uint8_t>(it.status == 0 ? 0 : 1));
-      if (it.status != 0) {
-        e.num<int32_t>(it.status);
-        continue;
-      }
-      e.num<uint8_t>(static_cast<uint8_t>(it.copies.size()));
-      for (auto& c : it.copies) {
-        auto& sh = c.shards[0];
-        e.num<uint16_t>(pool_idx[sh.pool_id]);
-        e.num<uint64_t>(sh.offset);
-      }
-    }
-    return std::move(e.buf);
+      wire::append_item(out, table, it.status, it.copies);
+    return wire::encode_put_start2_response(out);
   });
   rpc_.register_handler(M::BATCH_GET_WORKERS2, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
     if (!ks.is_leader())
       return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
-    serde::Dec d(b.data(), b.size());
-    uint32_t count = d.num<uint32_t>();
-    std::vector<std::string> keys(count);
-    for (uint32_t i = 0; i < count; ++i) keys[i] = d.str();
-    if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad v2 request"};
-    auto resp = ks.batch_get_workers(keys);
+    auto keys = wire::decode_get_workers2_request(b);
+    if (!keys.ok()) return keys.error();
+    auto resp = ks.batch_get_workers(keys.value());
 
-    serde::Enc e;
-    std::map<std::string, uint16_t> pool_idx;
-    std::vector<const std::string*> table;
-    for (auto& it : resp.items)
-      for (auto& c : it.info.copies)
-        for (auto& sh : c.shards)
-          if (pool_idx.emplace(sh.pool_id, static_cast<uint16_t>(table.size())).second)
-            table.push_back(&sh.pool_id);
-    e.num<uint16_t>(static_cast<uint16_t>(table.size()));
-    for (auto* p2 : table) e.str(*p2);
+    wire::BatchPlacements out;
+    wire::PoolTable table(out.pools);
     for (auto& it : resp.items) {
       // multi-shard copies cannot be encoded in v2 — signal fallback
-      bool multi = false;
+      int32_t status = it.status;
       for (auto& c : it.info.copies)
-        if (c.shards.size() != 1) multi = true;
-      if (it.status != 0 || multi) {
-        e.num<uint8_t>(1);
-        e.num<int32_t>(it.status != 0
-                           ? it.status
-                           : static_cast<int32_t>(ErrorCode::NOT_IMPLEMENTED));
-        continue;
-      }
-      e.num<uint8_t>(0);
-      e.num<uint64_t>(it.info.size);
-      e.num<uint64_t>(it.info.checksum);
-      e.num<uint8_t>(static_cast<uint8_t>(it.info.copies.size()));
-      for (auto& c : it.info.copies) {
-        e.num<uint16_t>(pool_idx[c.shards[0].pool_id]);
-        e.num<uint64_t>(c.shards[0].offset);
-      }
+        if (status == 0 && c.shards.size() != 1)
+          status = static_cast<int32_t>(ErrorCode::NOT_IMPLEMENTED);
+      wire::append_item(out, table, status, it.info.copies, it.info.size,
+                        it.info.checksum);
     }
-    return std::move(e.buf);
+    return wire::encode_get_workers2_response(out);
   });
   rpc_.register_handler(M::BATCH_UPSERT_START, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    serde::Dec d(b.data(), b.size());
-    uint64_t token = d.num<uint64_t>();
-    if (!d.ok()) return Error{ErrorCode::PROTOCOL_ERROR, "bad upsert request"};
-    BB_RETURN_IF_ERROR(ks.upsert_start_token(token));
+    auto token = wire::decode_upsert_start(b);
+    if (!token.ok()) return token.error();
+    BB_RETURN_IF_ERROR(ks.upsert_start_token(token.value()));
     return std::string{};
   });
   rpc_.register_handler(M::BATCH_COMMIT_TOKEN, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    serde::Dec d(b.data(), b.size());
-    uint64_t token = d.num<uint64_t>();
-    uint8_t flags = d.num<uint8_t>();  // bit 0: release session after commit
-    uint32_t n = d.num<uint32_t>();
-    if (!d.ok() || d.remaining() != n * sizeof(uint64_t) || n > (1u << 24))
-      return Error{ErrorCode::PROTOCOL_ERROR, "bad commit request"};
-    std::vector<uint64_t> digests(n);
-    for (uint32_t i = 0; i < n; ++i) digests[i] = d.num<uint64_t>();
-    BB_RETURN_IF_ERROR(ks.commit_token(token, digests, flags & 1));
+    auto c = wire::decode_commit_token(b);
+    if (!c.ok()) return c.error();
+    BB_RETURN_IF_ERROR(ks.commit_token(c->token, c->digests, c->flags & 1));
     return std::string{};
   });
   rpc_.register_handler(M::BATCH_REMOVE, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {

@@ -497,6 +497,111 @@ class TestGpuClientPaths:
         finally:
             cl.stop()
 
+    def test_sdma_fallback_roundtrip(self):
+        """set_fused_copy(False): every transfer rides hipMemcpyAsync on the
+        rotating streams and digests come from the separate batched checksum
+        launch. Covers the compact batch path (one worker) and the striped
+        multi-shard put/get halves (two workers)."""
+        g = bb.core.gpu
+        cl = Cluster(n_workers=1, pool_bytes=64 * MB,
+                     storage_class=bb.StorageClass.RAM_GPU)
+        try:
+            c = cl.client()
+            gcl = bb.GpuClient(c, 0)
+            gcl.init()
+            gcl.set_fused_copy(False)
+            sizes = [1, 1023, 4096, 65536 + 17]
+            buf = g.malloc(1 * MB)
+            dst = g.malloc(1 * MB)
+            blobs, puts, gets = [], [], []
+            off = 0
+            for i, s in enumerate(sizes):
+                b = os.urandom(s)
+                g.upload(buf + off, b)
+                blobs.append(b)
+                puts.append(("sdma%d" % i, buf + off, s))
+                gets.append(("sdma%d" % i, dst + off, s))
+                off += (s + 255) // 256 * 256  # keep 16B alignment
+            assert gcl.batch_put_device(puts) == [0] * len(sizes)
+            assert gcl.batch_get_device(gets, verify=True) == [0] * len(sizes)
+            ks = cl.keystone.service()
+            for (key, ptr, s), b in zip(gets, blobs):
+                assert g.download(ptr, s) == b, key
+                assert ks.get_workers(key).checksum == g.checksum_cpu(b), key
+            c.close()
+            g.free(buf)
+            g.free(dst)
+        finally:
+            cl.stop()
+        cl = Cluster(n_workers=2, pool_bytes=64 * MB,
+                     storage_class=bb.StorageClass.RAM_GPU)
+        try:
+            c = cl.client()
+            gcl = bb.GpuClient(c, 0)
+            gcl.init()
+            gcl.set_fused_copy(False)
+            S = 8 * MB
+            src = g.malloc(S)
+            dst = g.malloc(S)
+            blob = os.urandom(S)
+            g.upload(src, blob)
+            cfg = bb.PlacementConfig()
+            cfg.max_workers_per_copy = 2
+            assert gcl.batch_put_device([("sdma-striped", src, S)], cfg) == [0]
+            info = cl.keystone.service().get_workers("sdma-striped")
+            assert len(info.copies[0].shards) == 2
+            assert info.checksum == g.checksum_cpu(blob)
+            assert gcl.batch_get_device([("sdma-striped", dst, S)],
+                                        verify=True) == [0]
+            assert g.download(dst, S) == blob
+            c.close()
+            g.free(src)
+            g.free(dst)
+        finally:
+            cl.stop()
+
+    def test_unaligned_buffers_roundtrip(self):
+        """Sources and destinations 8 bytes off 16-byte alignment take the
+        copy-only kernel plus a separate digest launch instead of the fused
+        copy+digest kernel. Every size stays below one 1 KiB digest tile, so
+        only the byte-guarded fragment loads and the byte loop of the copy
+        kernel touch the misaligned addresses."""
+        cl = Cluster(n_workers=1, pool_bytes=64 * MB,
+                     storage_class=bb.StorageClass.RAM_GPU)
+        g = bb.core.gpu
+        try:
+            c = cl.client()
+            gcl = bb.GpuClient(c, 0)
+            gcl.init()
+            sizes = [1, 100, 1023]
+            buf = g.malloc(1 * MB)
+            dst = g.malloc(1 * MB)
+            assert buf % 16 == 0 and dst % 16 == 0
+            blobs, puts, gets = [], [], []
+            off = 8
+            for i, s in enumerate(sizes):
+                b = os.urandom(s)
+                g.upload(buf + off, b)
+                blobs.append(b)
+                puts.append(("unal%d" % i, buf + off, s))
+                gets.append(("unal%d" % i, dst + off, s))
+                off += 4096
+            assert gcl.batch_put_device(puts) == [0] * len(sizes)
+            hc = cl.client(verify_checksum_on_get=True)
+            ks = cl.keystone.service()
+            for (key, _, _), b in zip(puts, blobs):
+                assert hc.get(key) == b, key
+                assert ks.get_workers(key).checksum == g.checksum_cpu(b), key
+            assert gcl.batch_get_device(gets, verify=True) == [0, 0, 0]
+            for (key, ptr, s), b in zip(gets, blobs):
+                assert g.download(ptr, s) == b, key
+            hc.close()
+            c.close()
+            g.free(buf)
+            g.free(dst)
+        finally:
+            cl.stop()
+
 
 class TestGpuReplication:
     def test_device_put_replicated_single_worker(self):
