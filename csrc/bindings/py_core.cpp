@@ -560,6 +560,37 @@ PYBIND11_MODULE(_core, m) {
                                            out.data(), device, nullptr));
            return out;
          }, py::arg("objs"), py::arg("device") = 0);
+  using DescTuples = std::vector<std::tuple<uint64_t, uint64_t, uint64_t>>;
+  auto to_put_descs = [](const DescTuples& descs) {
+    std::vector<gpu::PutDesc> ds;
+    for (auto& [src, dst, n] : descs)
+      ds.push_back({reinterpret_cast<const void*>(src),
+                    reinterpret_cast<void*>(dst), n});
+    return ds;
+  };
+  gm.def("fused_put", [to_put_descs](const DescTuples& descs) {
+    auto ds = to_put_descs(descs);
+    // poisoned: finalize(0, 0) is 0, so a digest that was never written
+    // must not pass for the digest of an empty object
+    std::vector<uint64_t> out(ds.size(), ~0ull);
+    py::gil_scoped_release rel;
+    unwrap_void(gpu::fused_put(ds.data(), static_cast<uint32_t>(ds.size()),
+                               out.data(), nullptr));
+    return out;
+  });
+  // one FusedPutPlan, replayed `steps` times: one digest list per step
+  gm.def("fused_put_plan",
+         [to_put_descs](const DescTuples& descs, int steps, int device) {
+           auto ds = to_put_descs(descs);
+           std::vector<std::vector<uint64_t>> out(
+               steps, std::vector<uint64_t>(ds.size()));
+           py::gil_scoped_release rel;
+           gpu::FusedPutPlan plan;
+           unwrap_void(plan.build(ds.data(), static_cast<uint32_t>(ds.size()),
+                                  device));
+           for (auto& step : out) unwrap_void(plan.run(step.data()));
+           return out;
+         }, py::arg("descs"), py::arg("steps"), py::arg("device") = 0);
   gm.def("batched_copy",
          [](const std::vector<std::tuple<uint64_t, uint64_t, uint64_t>>& descs) {
            std::vector<gpu::CopyDesc> ds;

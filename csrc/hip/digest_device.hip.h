@@ -1,17 +1,34 @@
-// Device-side bbhash64 building blocks shared by the standalone checksum
-// kernels (checksum.hip) and the fused copy+digest put kernel (memops.hip).
-// Spec: csrc/include/blackbird/gpu/digest_spec.h.
+// Device-side building blocks of the batched kernels: the bbhash64 tile
+// helpers, the prefix search, and the tile walk shared by the hash-only and
+// the fused copy+digest kernel (digest.hip; batched_copy in memops.hip uses
+// the search). Spec: csrc/include/blackbird/gpu/digest_spec.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "blackbird/gpu/digest_spec.h"
+#include "blackbird/gpu/gpu_kernels.h"
 
 namespace blackbird::gpu::dev {
 
 using i32x4 = __attribute__((__vector_size__(16))) int;
 using i32x16 = __attribute__((__vector_size__(64))) int;
 using namespace blackbird::digest;
+
+constexpr int kBlock = 256;  // 4 waves
+constexpr int kWavesPerBlock = kBlock / 64;
+
+// Largest i with prefix[i] <= c (prefix is non-decreasing, prefix[0] == 0).
+__device__ inline uint32_t find_seg(const uint64_t* __restrict__ prefix,
+                                    uint32_t n, uint64_t c) {
+  uint32_t lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (prefix[mid] <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
 
 // Per-lane B fragment: 16 bytes B[k][c] with c = lane&31, k = (lane>>5)*16+j.
 __device__ inline i32x4 make_b_frag(int lane) {
@@ -92,6 +109,101 @@ __device__ inline uint64_t hash_tile_frag(const i32x4& a_frag,
   i32x16 acc = {};
   acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, acc, 0, 0, 0);
   return fold_tile(acc, wr, slot);
+}
+
+// The batched tile walk. One desc = one whole object at object-offset 0;
+// tile_prefix[i] is the global index of object i's first 1-KiB tile. Each
+// wave owns a CONTIGUOUS range of global tiles, so object switches (a
+// 64-lane reduction + one atomic) happen only at object boundaries inside
+// the range; the current object's descriptor/boundary live in registers (a
+// per-tile global load of descs[]/tile_prefix[] serializes on L2 latency).
+// Every tile is loaded once with the MFMA A-fragment lane map (fully
+// coalesced) and hashed in registers; out[i] accumulates object i's partial
+// sums and is finalized by a follow-up kernel.
+//   kCopy:     also store the fragment to dst with the same lane map.
+//   kPrefetch: software pipeline — the NEXT full tile's fragment loads while
+//              the current one is stored+hashed, so the VALU fold hides the
+//              load latency.
+template <bool kCopy, bool kPrefetch>
+__device__ __forceinline__ void digest_walk(
+    const CopyDesc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
+    uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const uint64_t gwave =
+      static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
+  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
+  const uint64_t per = (total_tiles + nwaves - 1) / nwaves;
+  const uint64_t begin = gwave * per;
+  const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
+  if (begin >= total_tiles) return;
+
+  const i32x4 b_frag = make_b_frag(lane);
+  const WReg wr = make_w_reg(lane);
+  const uint32_t lane_off = lane_tile_offset(lane);
+
+  uint32_t oi = find_seg(tile_prefix, nobjs, begin);
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t nbytes, cur_full;
+  auto enter_object = [&] {
+    const CopyDesc d = descs[oi];
+    src = static_cast<const uint8_t*>(d.src);
+    dst = static_cast<uint8_t*>(d.dst);
+    nbytes = d.nbytes;
+    cur_full = nbytes / kTileBytes;
+  };
+  enter_object();
+  uint64_t base_tile = tile_prefix[oi];
+  uint64_t next_boundary = (oi + 1 < nobjs) ? tile_prefix[oi + 1] : ~0ull;
+
+  uint64_t h = 0;
+  bool have_pre = false;
+  i32x4 pre{};
+  for (uint64_t gt = begin; gt < end; ++gt) {
+    while (gt >= next_boundary) {
+      h = wave_sum_u64(h);
+      if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
+      h = 0;
+      ++oi;
+      enter_object();
+      base_tile = next_boundary;
+      next_boundary = (oi + 1 < nobjs) ? tile_prefix[oi + 1] : ~0ull;
+      have_pre = false;  // prefetch belonged to the previous object
+    }
+    const uint64_t t = gt - base_tile;
+    const uint64_t toff = t * kTileBytes;
+    i32x4 a;
+    if (t < cur_full) {
+      if constexpr (kPrefetch) {
+        a = have_pre ? pre : load_a_frag(src + toff, lane);
+        have_pre = (gt + 1 < end) && (gt + 1 < next_boundary) &&
+                   (t + 1 < cur_full);
+        if (have_pre) pre = load_a_frag(src + toff + kTileBytes, lane);
+      } else {
+        a = load_a_frag(src + toff, lane);
+      }
+      // nontemporal: an A/B test against a temporal (L2-filling) store was
+      // within run variance end-to-end; the 1000-step soak record stands on
+      // this version
+      if constexpr (kCopy)
+        __builtin_nontemporal_store(
+            a, reinterpret_cast<i32x4*>(dst + toff + lane_off));
+    } else {
+      // tail tile: zero-padded hash, byte-guarded store
+      a = load_a_frag_guarded(src, toff, nbytes, lane);
+      if constexpr (kCopy) {
+        const uint64_t base = toff + lane_off;
+        const int8_t* ab = reinterpret_cast<const int8_t*>(&a);
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (base + j < nbytes) dst[base + j] = static_cast<uint8_t>(ab[j]);
+      }
+    }
+    h += hash_tile_frag(a, b_frag, wr, t * 64 + lane);
+  }
+  h = wave_sum_u64(h);
+  if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
 }
 
 }  // namespace blackbird::gpu::dev

@@ -1,5 +1,5 @@
 // Specification of the Blackbird-MI355X object digest ("bbhash64").
-// Shared by the CDNA4 MFMA kernel (csrc/hip/checksum.hip) and the exact CPU
+// Shared by the CDNA4 MFMA kernel (csrc/hip/digest.hip) and the exact CPU
 // reference (csrc/common/checksum_cpu.cpp) — all math is wraparound u64/u32
 // and fully commutative, so GPU and CPU produce identical bits regardless of
 // execution order.

@@ -59,25 +59,22 @@ Result<void> mfma_i8_probe(const int8_t* host_a, const int8_t* host_b,
 
 // ------------------------------------------- batched scatter/gather copy
 // One launch serves a whole batch of object transfers (the fused multi-object
-// path behind batch_put/batch_get). Descriptors are copied to device memory
-// by the caller.
+// path behind batch_put/batch_get). CopyDesc is the one descriptor of every
+// batched kernel, on host and device.
 struct CopyDesc {
   const void* src;
   void* dst;
   uint64_t nbytes;
 };
-// descs: HOST array of n descriptors (the implementation stages them).
+// descs: HOST array of n descriptors (the implementation stages them and
+// uploads them on `stream`). Returns once the work is enqueued.
 Result<void> batched_copy(const CopyDesc* descs, uint32_t n, hipStream_t stream);
 
 // Fused put: copy whole single-shard objects (src→dst, both device-local,
 // 16B-aligned) AND compute their bbhash64 digests in ONE kernel — the data
 // is read once instead of twice (copy + hash). out_digests: HOST array
 // (call blocks on `stream`).
-struct PutDesc {
-  const void* src;
-  void* dst;
-  uint64_t nbytes;
-};
+using PutDesc = CopyDesc;
 Result<void> fused_put(const PutDesc* descs, uint32_t n, uint64_t* out_digests,
                        hipStream_t stream);
 
@@ -111,7 +108,8 @@ Result<void> fill_pattern(void* dev_ptr, uint64_t nbytes, uint64_t seed,
 Result<uint64_t> verify_pattern(const void* dev_ptr, uint64_t nbytes, uint64_t seed,
                                 hipStream_t stream);  // returns #mismatched u64
 
-// Synchronous copy on a per-thread NON-BLOCKING stream. The library never
+// Synchronous copy on one stream of a shared pool of NON-BLOCKING streams
+// (held under that stream's mutex for the call). The library never
 // issues work on the legacy (null) stream: ROCm fails legacy-stream ops in
 // EVERY thread while any hipGraph capture is open (sessions capture their
 // step graphs lazily), so all blocking copies route through here. kind is a

@@ -50,3 +50,9 @@ if mode == "hashbw":
     for _ in range(3): g.batched_copy(descs)
     dt=(_t.perf_counter()-t0)/3
     print(f"batched_copy 1024x1MB: {half/dt/1e9:.0f} GB/s payload ({2*half/dt/1e9:.0f} GB/s HBM)")
+    # fused copy+digest kernel, same descriptors
+    g.fused_put(descs)
+    t0=_t.perf_counter()
+    for _ in range(3): g.fused_put(descs)
+    dt=(_t.perf_counter()-t0)/3
+    print(f"fused_put 1024x1MB: {half/dt/1e9:.0f} GB/s payload ({2*half/dt/1e9:.0f} GB/s HBM)")

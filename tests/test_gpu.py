@@ -86,6 +86,126 @@ class TestChecksumKernel:
             gpu.free(ptr)
 
 
+class _PutCase:
+    """One size list laid out for the fused-put tests: every object at a
+    16-byte-aligned offset of one allocation with a 16-byte gap after it.
+    Source gaps hold 0x5A, the destination is pre-filled with 0xA5, so a
+    store past an object's end shows up in `dst_image`. Built once per size
+    list (CPU digests included) and shared, read-only, by all entry points."""
+    PAD = 0xA5
+
+    def __init__(self, sizes):
+        rng = np.random.default_rng(1000003 * len(sizes) + sum(sizes))
+        self.sizes = list(sizes)
+        self.offs = []
+        off = 0
+        for s in sizes:
+            self.offs.append(off)
+            off += (s + 15) // 16 * 16 + 16
+        self.span = off
+        self.blobs = [rng.integers(0, 256, size=s, dtype=np.uint8).tobytes()
+                      for s in sizes]
+        self.want = [gpu.checksum_cpu(b) for b in self.blobs]
+        src = bytearray(b"\x5a" * self.span)
+        dst = bytearray(bytes([self.PAD]) * self.span)
+        for o, b in zip(self.offs, self.blobs):
+            src[o:o + len(b)] = b
+            dst[o:o + len(b)] = b
+        self.src_image = bytes(src)
+        self.dst_image = bytes(dst)
+
+
+_put_cases = {}
+
+
+def _put_case(sizes):
+    key = tuple(sizes)
+    if key not in _put_cases:
+        _put_cases[key] = _PutCase(sizes)
+    return _put_cases[key]
+
+
+# name -> size list; what each exercises is spelled out next to it
+PUT_SIZE_LISTS = {
+    # one guarded tile, and nothing else for the grid to do
+    "one_byte": [1],
+    # one full tile, no tail, and the prefetch has nothing to fetch
+    "one_tile": [1024],
+    # tails on either side of a tile edge; an object boundary directly
+    # after a prefetched tile
+    "tile_edges": [1023, 1025, 16, 17, 2048, 3077],
+    # more objects than any wave has tiles: every wave crosses a boundary
+    "many_small": [100] * 300,
+    # empty objects leading, consecutive and trailing
+    "with_empties": [0, 4096, 0, 0, 777, 0],
+    # just over 32768 tiles: the 4096-block cap binds, 3 tiles per wave
+    "grid_cap": [8 * MB + 1, 3, 12 * MB + 1023, 1 * MB, 12 * MB + 512],
+}
+
+
+class TestFusedPutKernel:
+    """fused_put / FusedPutPlan at kernel level, next to the hash-only batch
+    kernel they share their tile walk with: digests bit-exact against the
+    CPU reference, bytes copied exactly, nothing stored past an object."""
+
+    def _run(self, sizes, entry):
+        case = _put_case(sizes)
+        src, dst = gpu.malloc(case.span), gpu.malloc(case.span)
+        try:
+            gpu.upload(src, case.src_image)
+            gpu.upload(dst, bytes([case.PAD]) * case.span)
+            # an empty object is a non-null pointer with size 0
+            descs = [(src + o, dst + o, s)
+                     for o, s in zip(case.offs, case.sizes)]
+            if entry == "checksum_device_batch":
+                steps = [gpu.checksum_device_batch(
+                    [(s, n) for s, _, n in descs])]
+            elif entry == "fused_put":
+                steps = [gpu.fused_put(descs)]
+            else:
+                steps = gpu.fused_put_plan(descs, 2)
+                assert len(steps) == 2
+                # accumulators are reset inside the captured graph
+                assert steps[1] == steps[0]
+            for got in steps:
+                bad = [i for i, (g_, w) in enumerate(zip(got, case.want))
+                       if g_ != w]
+                assert len(got) == len(case.want) and not bad, (entry, bad[:8])
+            if entry != "checksum_device_batch":
+                # every object's bytes landed; every gap byte and every byte
+                # past an object's end still holds the pre-fill
+                assert gpu.download(dst, case.span) == case.dst_image, entry
+        finally:
+            gpu.free(src)
+            gpu.free(dst)
+
+    @pytest.mark.parametrize("name", list(PUT_SIZE_LISTS))
+    def test_checksum_device_batch(self, name):
+        self._run(PUT_SIZE_LISTS[name], "checksum_device_batch")
+
+    @pytest.mark.parametrize("name", list(PUT_SIZE_LISTS))
+    def test_fused_put(self, name):
+        self._run(PUT_SIZE_LISTS[name], "fused_put")
+
+    @pytest.mark.parametrize("name", list(PUT_SIZE_LISTS))
+    def test_fused_put_plan(self, name):
+        self._run(PUT_SIZE_LISTS[name], "fused_put_plan")
+
+    def test_all_empty_batch(self):
+        """Every object empty: both one-shot entry points return the digest
+        of the empty string per object (digest_spec.h); a plan refuses."""
+        buf = gpu.malloc(64)
+        try:
+            want = [gpu.checksum_cpu(b"")] * 2
+            assert gpu.checksum_device_batch([(buf, 0), (buf + 16, 0)]) == want
+            descs = [(buf, buf + 32, 0), (buf + 16, buf + 48, 0)]
+            assert gpu.fused_put(descs) == want
+            with pytest.raises(Exception, match="INVALID_ARGUMENT"):
+                gpu.fused_put_plan(descs, 2)
+        finally:
+            gpu.free(buf)
+
+
 class TestMemops:
     def test_fill_verify(self):
         n = 8 * MB
@@ -99,21 +219,25 @@ class TestMemops:
 
     def test_batched_copy(self):
         rng = np.random.default_rng(3)
-        sizes = [4096, 1 * MB, 100, 256 * 1024 + 13]
-        srcs, dsts, blobs = [], [], []
+        # 0 in the middle: a descriptor that owns no chunk; 4097: one full
+        # 4 KiB chunk plus a 1-byte chunk
+        sizes = [4096, 1 * MB, 0, 100, 256 * 1024 + 13, 4097, 5000]
+        src_skew = [0, 0, 0, 0, 0, 0, 1]  # last one takes the unaligned branch
+        bases, srcs, dsts, blobs = [], [], [], []
         try:
-            for s in sizes:
+            for s, k in zip(sizes, src_skew):
                 blob = rng.integers(0, 256, size=s, dtype=np.uint8).tobytes()
-                sp, dp = gpu.malloc(s), gpu.malloc(s)
-                gpu.upload(sp, blob)
-                srcs.append(sp)
+                sp, dp = gpu.malloc(s + 16), gpu.malloc(s + 16)
+                bases += [sp, dp]
+                gpu.upload(sp + k, blob)
+                srcs.append(sp + k)
                 dsts.append(dp)
                 blobs.append(blob)
             gpu.batched_copy([(srcs[i], dsts[i], sizes[i]) for i in range(len(sizes))])
             for i, s in enumerate(sizes):
                 assert gpu.download(dsts[i], s) == blobs[i], i
         finally:
-            for p in srcs + dsts:
+            for p in bases:
                 gpu.free(p)
 
 
