@@ -578,6 +578,48 @@ PYBIND11_MODULE(_core, m) {
                                out.data(), nullptr));
     return out;
   });
+  // striped copy+digest: segs are (src, dst, nbytes, first_tile, obj) tuples;
+  // returns (segment digests, object digests)
+  using SegTuples =
+      std::vector<std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint32_t>>;
+  auto to_stripe_segs = [](const SegTuples& segs) {
+    std::vector<gpu::StripeSeg> ss;
+    for (auto& [src, dst, n, first_tile, obj] : segs)
+      ss.push_back({reinterpret_cast<const void*>(src),
+                    reinterpret_cast<void*>(dst), n, first_tile, obj});
+    return ss;
+  };
+  gm.def("fused_stripe", [to_stripe_segs](const SegTuples& segs,
+                                          const std::vector<uint64_t>& obj_sizes) {
+    auto ss = to_stripe_segs(segs);
+    // poisoned, as in fused_put
+    std::vector<uint64_t> seg_out(ss.size(), ~0ull);
+    std::vector<uint64_t> obj_out(obj_sizes.size(), ~0ull);
+    py::gil_scoped_release rel;
+    unwrap_void(gpu::fused_stripe(ss.data(), static_cast<uint32_t>(ss.size()),
+                                  obj_sizes.data(),
+                                  static_cast<uint32_t>(obj_sizes.size()),
+                                  seg_out.data(), obj_out.data(), nullptr));
+    return std::make_pair(seg_out, obj_out);
+  }, py::arg("segs"), py::arg("obj_sizes"));
+  // the argument check of fused_stripe alone (no GPU): raises INVALID_ARGUMENT
+  gm.def("check_stripe_segs", [to_stripe_segs](const SegTuples& segs,
+                                               const std::vector<uint64_t>& obj_sizes) {
+    auto ss = to_stripe_segs(segs);
+    unwrap_void(gpu::check_stripe_segs(ss.data(), static_cast<uint32_t>(ss.size()),
+                                       obj_sizes.data(),
+                                       static_cast<uint32_t>(obj_sizes.size())));
+  }, py::arg("segs"), py::arg("obj_sizes"));
+  // one copy's shard lengths → [(offset, nbytes, first_tile)], None = not fusable
+  gm.def("plan_stripe", [](uint64_t obj_size, const std::vector<uint64_t>& shard_lens)
+                            -> std::optional<std::vector<
+                                std::tuple<uint64_t, uint64_t, uint64_t>>> {
+    auto plan = gpu::plan_stripe(obj_size, shard_lens);
+    if (!plan) return std::nullopt;
+    std::vector<std::tuple<uint64_t, uint64_t, uint64_t>> out;
+    for (const auto& p : *plan) out.emplace_back(p.offset, p.nbytes, p.first_tile);
+    return out;
+  }, py::arg("obj_size"), py::arg("shard_lens"));
   // one FusedPutPlan, replayed `steps` times: one digest list per step
   gm.def("fused_put_plan",
          [to_put_descs](const DescTuples& descs, int steps, int device) {

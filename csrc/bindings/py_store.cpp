@@ -505,6 +505,10 @@ void bind_store(py::module_& m) {
              return true;
            }, py::arg("batch"), py::arg("verify") = false)
       .def_property_readonly("session_put_steps", &GpuClient::session_put_steps)
+      .def_property_readonly("striped_fused_items",
+                             &GpuClient::striped_fused_items)
+      .def_property_readonly("striped_fused_get_items",
+                             &GpuClient::striped_fused_get_items)
       .def_property_readonly("session_get_steps", &GpuClient::session_get_steps)
       .def_property_readonly("session_graph_steps",
                              &GpuClient::session_graph_steps)

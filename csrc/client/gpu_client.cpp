@@ -317,6 +317,67 @@ struct GpuClient::Router {
   }
 };
 
+// The striped items of one v1 batch that ride ONE gpu::fused_stripe launch:
+// every shard is a segment, every copy one kernel "object" — the launch
+// moves the bytes and yields each shard's digest and each copy's object
+// digest from a single read. A copy joins only when the planner accepts its
+// shard lengths and every shard resolves to a 16B-aligned device pointer;
+// the caller routes everything else the general way.
+struct GpuClient::StripeBatch {
+  struct Entry {
+    uint32_t item;
+    uint32_t first_obj, ncopies;  // kernel objects [first_obj, +ncopies)
+    uint32_t first_seg;           // segments of copy 0, copy 1, … back to back
+  };
+  std::vector<gpu::StripeSeg> segs;
+  std::vector<uint64_t> obj_sizes;
+  std::vector<Entry> entries;
+  std::vector<uint64_t> seg_digests, obj_digests;  // run() output
+
+  // All of `copy` as one new kernel object, `user` holding the object's
+  // bytes back to back (Put: the source; get: the destination). false =
+  // not fusable, nothing added.
+  template <bool Put>
+  bool add_copy(GpuClient& g, std::conditional_t<Put, const uint8_t*, uint8_t*> user,
+                uint64_t size, const CopyPlacement& copy) {
+    std::vector<uint64_t> lens;
+    lens.reserve(copy.shards.size());
+    for (const auto& s : copy.shards) lens.push_back(s.length);
+    const auto plan = gpu::plan_stripe(size, lens);
+    if (!plan) return false;
+    const size_t mark = segs.size();
+    const uint32_t obj = static_cast<uint32_t>(obj_sizes.size());
+    for (size_t k = 0; k < plan->size(); ++k) {
+      uint8_t* pool_ptr = g.resolve_device_ptr(copy.shards[k]);
+      if (!pool_ptr || !aligned16(pool_ptr, user + (*plan)[k].offset)) {
+        segs.resize(mark);
+        return false;
+      }
+      auto* slice = const_cast<uint8_t*>(user) + (*plan)[k].offset;
+      if constexpr (Put)
+        segs.push_back({slice, pool_ptr, (*plan)[k].nbytes, (*plan)[k].first_tile, obj});
+      else
+        segs.push_back({pool_ptr, slice, (*plan)[k].nbytes, (*plan)[k].first_tile, obj});
+    }
+    obj_sizes.push_back(size);
+    return true;
+  }
+  // drop everything added since the marks (an item whose later copy failed)
+  void rewind(size_t seg_mark, size_t obj_mark) {
+    segs.resize(seg_mark);
+    obj_sizes.resize(obj_mark);
+  }
+  // the launch (synchronizes `stream` itself); no launch for an empty batch
+  Result<void> run(hipStream_t stream) {
+    seg_digests.assign(segs.size(), 0);
+    obj_digests.assign(obj_sizes.size(), 0);
+    return gpu::fused_stripe(segs.data(), static_cast<uint32_t>(segs.size()),
+                             obj_sizes.data(),
+                             static_cast<uint32_t>(obj_sizes.size()),
+                             seg_digests.data(), obj_digests.data(), stream);
+  }
+};
+
 // One batched digest launch over items[indices]: out[j] is the digest of
 // ptr_of(indices[j]) .. + size_of(indices[j]). No launch for an empty list.
 template <typename PtrOf, typename SizeOf>
@@ -1082,6 +1143,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
 
   std::vector<int32_t> statuses(items.size(), 0);
   Router<true> rt(*this, fused_copy_, /*defer=*/false);
+  StripeBatch stripes;
 
   for (size_t i = 0; i < items.size(); ++i) {
     auto& placed = start->items[i];
@@ -1100,6 +1162,29 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
         continue;
       }
     }
+    // striped fast path: every shard of every copy device-visible and on a
+    // tile boundary of the object → the item rides the fused_stripe launch
+    // (copy, per-shard digests and object digest from one read)
+    if (fused_copy_ && cfg.checksum && aligned16(items[i].ptr)) {
+      bool striped = false;
+      for (const auto& copy : placed.copies)
+        if (copy.shards.size() > 1) striped = true;
+      const size_t seg_mark = stripes.segs.size();
+      const size_t obj_mark = stripes.obj_sizes.size();
+      bool all = striped;
+      for (size_t c = 0; c < placed.copies.size() && all; ++c)
+        all = stripes.add_copy<true>(*this,
+                                     static_cast<const uint8_t*>(items[i].ptr),
+                                     items[i].size, placed.copies[c]);
+      if (all) {
+        stripes.entries.push_back({static_cast<uint32_t>(i),
+                                   static_cast<uint32_t>(obj_mark),
+                                   static_cast<uint32_t>(placed.copies.size()),
+                                   static_cast<uint32_t>(seg_mark)});
+        continue;
+      }
+      stripes.rewind(seg_mark, obj_mark);
+    }
     bool ok = true;
     for (const auto& copy : placed.copies)
       if (!(ok = rt.add_copy(static_cast<const uint8_t*>(items[i].ptr), copy,
@@ -1109,9 +1194,10 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
     else statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
   BB_RETURN_IF_ERROR(rt.launch_put(items, cfg.checksum));
+  BB_RETURN_IF_ERROR(stripes.run(streams_[2]));
 
-  // per-shard digests for striped copies (one batched launch hashes every
-  // source slice) — recorded server-side so the scrubber can verify each
+  // per-shard digests for striped copies that took the general route (one
+  // batched launch hashes every source slice) — recorded server-side so the scrubber can verify each
   // striped shard independently
   std::map<uint32_t, std::vector<std::vector<uint64_t>>> shard_digests;
   if (cfg.checksum) {
@@ -1151,6 +1237,27 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
           got.value()[k];
   }
 
+  // the fused_stripe items complete with the plain group: the object digest
+  // is copy 0's (replicas hashed the same source; one that disagrees saw it
+  // change mid-batch and must not commit), the shard digests are the
+  // launch's segment digests in copy, shard order
+  for (const auto& e : stripes.entries) {
+    const auto& copies = start->items[e.item].copies;
+    const uint64_t digest = stripes.obj_digests[e.first_obj];
+    for (uint32_t c = 1; c < e.ncopies; ++c)
+      if (stripes.obj_digests[e.first_obj + c] != digest)
+        statuses[e.item] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
+    auto& out = shard_digests[e.item];
+    out.resize(copies.size());
+    size_t k = e.first_seg;
+    for (uint32_t c = 0; c < copies.size(); ++c)
+      for (size_t s2 = 0; s2 < copies[c].shards.size(); ++s2)
+        out[c].push_back(stripes.seg_digests[k++]);
+    rt.plain_idx.push_back(e.item);
+    rt.plain_digests.push_back(digest);
+  }
+  striped_fused_items_.fetch_add(stripes.entries.size());
+
   BB_RETURN_IF_ERROR(complete_puts(items, rt, 1, &shard_digests, statuses,
                                    /*apply_statuses=*/true));
   cancel_failed(items, statuses);
@@ -1189,6 +1296,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
 
   std::vector<int32_t> statuses(items.size(), 0);
   Router<false> rt(*this, fused_copy_, /*defer=*/false);
+  StripeBatch stripes;
 
   for (size_t i = 0; i < items.size(); ++i) {
     auto& item = meta->items[i];
@@ -1200,14 +1308,34 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
       statuses[i] = static_cast<int32_t>(ErrorCode::SIZE_MISMATCH);
       continue;
     }
-    bool ok = false;
-    for (const auto& copy : item.info.copies)
+    // verified get of a striped copy: gathered AND hashed by the
+    // fused_stripe launch, so verification costs no second read
+    const bool stripe_ok = verify && fused_copy_ && item.info.checksum != 0 &&
+                           aligned16(items[i].ptr);
+    bool ok = false, striped = false;
+    for (const auto& copy : item.info.copies) {
+      if (stripe_ok && copy.shards.size() > 1 &&
+          stripes.add_copy<false>(*this, static_cast<uint8_t*>(items[i].ptr),
+                                  item.info.size, copy)) {
+        stripes.entries.push_back(
+            {static_cast<uint32_t>(i),
+             static_cast<uint32_t>(stripes.obj_sizes.size() - 1), 1, 0});
+        ok = striped = true;
+        break;
+      }
       if ((ok = rt.add_copy(static_cast<uint8_t*>(items[i].ptr), copy,
                             static_cast<uint32_t>(i)).ok()))
         break;  // first healthy copy wins
+    }
+    if (striped) continue;
     if (ok) rt.plain_idx.push_back(static_cast<uint32_t>(i));
     else statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
   }
+  BB_RETURN_IF_ERROR(stripes.run(streams_[2]));
+  for (const auto& e : stripes.entries)
+    if (stripes.obj_digests[e.first_obj] != meta->items[e.item].info.checksum)
+      statuses[e.item] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
+  striped_fused_get_items_.fetch_add(stripes.entries.size());
   BB_RETURN_IF_ERROR(rt.finish_get(
       items, verify,
       [&](uint32_t i) {

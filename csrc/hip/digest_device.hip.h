@@ -1,10 +1,13 @@
 // Device-side building blocks of the batched kernels: the bbhash64 tile
-// helpers, the prefix search, and the tile walk shared by the hash-only and
-// the fused copy+digest kernel (digest.hip; batched_copy in memops.hip uses
-// the search). Spec: csrc/include/blackbird/gpu/digest_spec.h.
+// helpers, the prefix search, and the tile walk shared by the hash-only
+// kernel, the fused copy+digest kernel (digest.hip) and the striped
+// copy+digest kernel (stripe.hip); batched_copy in memops.hip uses the
+// search. Spec: csrc/include/blackbird/gpu/digest_spec.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "blackbird/gpu/digest_spec.h"
 #include "blackbird/gpu/gpu_kernels.h"
@@ -61,15 +64,25 @@ __device__ inline WReg make_w_reg(int lane) {
   return r;
 }
 
-__device__ inline uint64_t fold_tile(const i32x16& acc, const WReg& wr,
-                                     uint64_t slot) {
+// The spec's group fold f(t,g) of this lane's 16 accumulators. It does not
+// depend on where the tile sits; position enters only through mix_slot.
+__device__ inline uint64_t fold_group(const i32x16& acc, const WReg& wr) {
   uint64_t f = 0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const uint32_t c32 = static_cast<uint32_t>(acc[j]);
     f += static_cast<uint64_t>(c32) * static_cast<uint64_t>(wr.w[j]);
   }
+  return f;
+}
+
+__device__ inline uint64_t mix_slot(uint64_t f, uint64_t slot) {
   return mix64(f + tile_weight(slot));
+}
+
+__device__ inline uint64_t fold_tile(const i32x16& acc, const WReg& wr,
+                                     uint64_t slot) {
+  return mix_slot(fold_group(acc, wr), slot);
 }
 
 // Lane's 16-byte offset within a 1024-B tile for the MFMA A-fragment map
@@ -103,31 +116,45 @@ __device__ inline uint64_t wave_sum_u64(uint64_t v) {
   return v;
 }
 
+// One MFMA and one group fold: everything of a tile's hash but its position.
+__device__ inline uint64_t fold_tile_frag(const i32x4& a_frag,
+                                          const i32x4& b_frag, const WReg& wr) {
+  i32x16 acc = {};
+  acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, acc, 0, 0, 0);
+  return fold_group(acc, wr);
+}
+
 __device__ inline uint64_t hash_tile_frag(const i32x4& a_frag,
                                           const i32x4& b_frag, const WReg& wr,
                                           uint64_t slot) {
-  i32x16 acc = {};
-  acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, acc, 0, 0, 0);
-  return fold_tile(acc, wr, slot);
+  return mix_slot(fold_tile_frag(a_frag, b_frag, wr), slot);
 }
 
-// The batched tile walk. One desc = one whole object at object-offset 0;
-// tile_prefix[i] is the global index of object i's first 1-KiB tile. Each
-// wave owns a CONTIGUOUS range of global tiles, so object switches (a
-// 64-lane reduction + one atomic) happen only at object boundaries inside
-// the range; the current object's descriptor/boundary live in registers (a
-// per-tile global load of descs[]/tile_prefix[] serializes on L2 latency).
-// Every tile is loaded once with the MFMA A-fragment lane map (fully
-// coalesced) and hashed in registers; out[i] accumulates object i's partial
-// sums and is finalized by a follow-up kernel.
+// The batched tile walk. One desc = one contiguous run of bytes that starts
+// on a tile boundary: a whole object at object-offset 0 (CopyDesc), or a
+// segment of a striped object (StripeSeg). tile_prefix[i] is the global index
+// of desc i's first 1-KiB tile. Each wave owns a CONTIGUOUS range of global
+// tiles, so desc switches (a 64-lane reduction + one atomic) happen only at
+// desc boundaries inside the range; the current descriptor/boundary live in
+// registers (a per-tile global load of descs[]/tile_prefix[] serializes on
+// L2 latency). Every tile is loaded once with the MFMA A-fragment lane map
+// (fully coalesced) and hashed in registers; out[i] accumulates desc i's
+// partial sums and is finalized by a follow-up kernel.
 //   kCopy:     also store the fragment to dst with the same lane map.
 //   kPrefetch: software pipeline — the NEXT full tile's fragment loads while
 //              the current one is stored+hashed, so the VALU fold hides the
 //              load latency.
-template <bool kCopy, bool kPrefetch>
+//   StripeSeg: the tile's group fold feeds two sums — out[i], slots counted
+//              from the segment's start, and obj_out[seg.obj], slots counted
+//              from the object's start (all 64-bit). A segment at tile 0 of
+//              its object has the same slots in both, so it runs one mix per
+//              tile and adds its one sum to both accumulators.
+template <bool kCopy, bool kPrefetch, typename Desc>
 __device__ __forceinline__ void digest_walk(
-    const CopyDesc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
-    uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out) {
+    const Desc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
+    uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out,
+    unsigned long long* __restrict__ obj_out = nullptr) {
+  constexpr bool kStripe = std::is_same_v<Desc, StripeSeg>;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const uint64_t gwave =
@@ -146,24 +173,39 @@ __device__ __forceinline__ void digest_walk(
   const uint8_t* src;
   uint8_t* dst;
   uint64_t nbytes, cur_full;
+  [[maybe_unused]] uint64_t first_slot = 0;  // StripeSeg: first_tile * 64
+  [[maybe_unused]] uint32_t obj = 0;
   auto enter_object = [&] {
-    const CopyDesc d = descs[oi];
+    const Desc d = descs[oi];
     src = static_cast<const uint8_t*>(d.src);
     dst = static_cast<uint8_t*>(d.dst);
     nbytes = d.nbytes;
     cur_full = nbytes / kTileBytes;
+    if constexpr (kStripe) {
+      first_slot = d.first_tile * 64;
+      obj = d.obj;
+    }
   };
   enter_object();
   uint64_t base_tile = tile_prefix[oi];
   uint64_t next_boundary = (oi + 1 < nobjs) ? tile_prefix[oi + 1] : ~0ull;
 
   uint64_t h = 0;
+  [[maybe_unused]] uint64_t ho = 0;  // StripeSeg: the object-slot sum
+  // StripeSeg, leaving a segment after h was reduced: the object's share
+  [[maybe_unused]] auto flush_object = [&] {
+    if (first_slot != 0) ho = wave_sum_u64(ho);  // wave-uniform
+    else ho = h;
+    if (lane == 0 && ho != 0) atomicAdd(&obj_out[obj], ho);
+    ho = 0;
+  };
   bool have_pre = false;
   i32x4 pre{};
   for (uint64_t gt = begin; gt < end; ++gt) {
     while (gt >= next_boundary) {
       h = wave_sum_u64(h);
       if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
+      if constexpr (kStripe) flush_object();
       h = 0;
       ++oi;
       enter_object();
@@ -200,10 +242,18 @@ __device__ __forceinline__ void digest_walk(
           if (base + j < nbytes) dst[base + j] = static_cast<uint8_t>(ab[j]);
       }
     }
-    h += hash_tile_frag(a, b_frag, wr, t * 64 + lane);
+    const uint64_t slot = t * 64 + lane;
+    if constexpr (kStripe) {
+      const uint64_t f = fold_tile_frag(a, b_frag, wr);
+      h += mix_slot(f, slot);
+      if (first_slot != 0) ho += mix_slot(f, first_slot + slot);  // wave-uniform
+    } else {
+      h += hash_tile_frag(a, b_frag, wr, slot);
+    }
   }
   h = wave_sum_u64(h);
   if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
+  if constexpr (kStripe) flush_object();
 }
 
 }  // namespace blackbird::gpu::dev

@@ -107,6 +107,11 @@ class GpuClient {
   uint64_t session_get_steps() const { return session_get_steps_; }
   // session steps that replayed the captured hipGraph (vs per-op launches)
   uint64_t session_graph_steps() const { return session_graph_steps_; }
+  // striped items moved by ONE fused_stripe launch (copy + shard digests +
+  // object digest in one pass) instead of copy + two digest launches (puts)
+  // or copy + verify launch (gets)
+  uint64_t striped_fused_items() const { return striped_fused_items_; }
+  uint64_t striped_fused_get_items() const { return striped_fused_get_items_; }
 
   // ---- pipelined batches: begin returns a token immediately; the batch
   // runs on a background thread (metadata RPCs of batch N+1 overlap the
@@ -170,6 +175,8 @@ class GpuClient {
   // routes a batch's transfers: fused copy list, SDMA streams or staging
   template <bool Put>
   struct Router;
+  // the striped items of a batch that ride one fused_stripe launch
+  struct StripeBatch;
   template <typename PtrOf, typename SizeOf>
   Result<std::vector<uint64_t>> digest_items(
       const std::vector<uint32_t>& indices, PtrOf ptr_of, SizeOf size_of,
@@ -247,6 +254,8 @@ class GpuClient {
   std::atomic<uint64_t> session_put_steps_{0};
   std::atomic<uint64_t> session_get_steps_{0};
   std::atomic<uint64_t> session_graph_steps_{0};
+  std::atomic<uint64_t> striped_fused_items_{0};
+  std::atomic<uint64_t> striped_fused_get_items_{0};
   // run the session desc list: captured-graph replay when available,
   // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
   // or a failed capture pins the session to the launch path)

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "blackbird/common/result.h"
+#include "blackbird/gpu/stripe_plan.h"
 
 // Forward decl to avoid pulling hip_runtime into every TU.
 struct ihipStream_t;
@@ -77,6 +78,20 @@ Result<void> batched_copy(const CopyDesc* descs, uint32_t n, hipStream_t stream)
 using PutDesc = CopyDesc;
 Result<void> fused_put(const PutDesc* descs, uint32_t n, uint64_t* out_digests,
                        hipStream_t stream);
+
+// Fused striped transfer: copy every segment src→dst (both device-visible,
+// 16B-aligned) AND compute, reading the data once, two digests — per segment
+// the bbhash64 of its bytes alone (what the keystone records per shard), per
+// object finalize(Σ checksum_cpu_tiles(segment bytes, first_tile), size) over
+// the segments naming it: the object's bbhash64 when they cover it exactly.
+// Segments of one object may sit anywhere in the list. The arguments go
+// through check_stripe_segs (stripe_plan.h) before any HIP call. obj_sizes
+// and both outputs are HOST arrays (call blocks on `stream`; nullptr = a
+// stream of the shared transfer pool). nseg == 0 returns at once.
+Result<void> fused_stripe(const StripeSeg* segs, uint32_t nseg,
+                          const uint64_t* obj_sizes, uint32_t nobj,
+                          uint64_t* out_seg_digests, uint64_t* out_obj_digests,
+                          hipStream_t stream);
 
 // Pre-instantiated fused-put step for batch sessions (fixed desc list every
 // step): descriptors live on-device (uploaded once by build), and the whole
