@@ -509,6 +509,8 @@ PYBIND11_MODULE(_core, m) {
   auto gm = m.def_submodule("gpu");
   gm.def("available", &gpu::available);
   gm.def("device_count", &gpu::device_count);
+  gm.def("digest_grid_waves", &gpu::digest_grid_waves, py::arg("total_tiles"));
+  gm.def("digest_walk_depth", &gpu::digest_walk_depth);
   gm.def("checksum_cpu_tiles", [](py::buffer b, uint64_t first_tile) {
     py::buffer_info info = b.request();
     return gpu::checksum_cpu_tiles(info.ptr,

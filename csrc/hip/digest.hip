@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(kBlock)
 bbhash64_batch_kernel(const CopyDesc* __restrict__ descs,
                       const uint64_t* __restrict__ tile_prefix, uint32_t nobjs,
                       uint64_t total_tiles, unsigned long long* __restrict__ out) {
-  digest_walk<false, false>(descs, tile_prefix, nobjs, total_tiles, out);
+  digest_walk<false, 0>(descs, tile_prefix, nobjs, total_tiles, out);
 }
 
 // Fused put: copy src→dst and hash, reading the data once.
@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(kBlock)
 fused_put_kernel(const CopyDesc* __restrict__ descs,
                  const uint64_t* __restrict__ tile_prefix, uint32_t nobjs,
                  uint64_t total_tiles, unsigned long long* __restrict__ out) {
-  digest_walk<true, true>(descs, tile_prefix, nobjs, total_tiles, out);
+  digest_walk<true, kWalkDepth>(descs, tile_prefix, nobjs, total_tiles, out);
 }
 
 __global__ void bbhash64_finalize_kernel(const CopyDesc* __restrict__ descs,
@@ -70,12 +70,13 @@ bbhash64_kernel(const uint8_t* __restrict__ data, uint64_t nbytes,
 
   const i32x4 b_frag = make_b_frag(lane);
   const WReg wr = make_w_reg(lane);
+  const uint32_t lane_off = lane_tile_offset(lane);
   uint64_t h = 0;
 
   for (uint64_t t = gwave; t < ntiles; t += stride) {
     i32x4 a_frag = (t < full_tiles)
-                       ? load_a_frag(data + t * kTileBytes, lane)
-                       : load_a_frag_guarded(data, t * kTileBytes, nbytes, lane);
+                       ? load_a_frag(data + t * kTileBytes, lane_off)
+                       : load_a_frag_guarded(data, t * kTileBytes, nbytes, lane_off);
     h += hash_tile_frag(a_frag, b_frag, wr, t * 64 + lane);
   }
 
@@ -143,6 +144,12 @@ int device_count() {
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
 }
+
+uint64_t digest_grid_waves(uint64_t total_tiles) {
+  return static_cast<uint64_t>(digest_grid(total_tiles)) * kWavesPerBlock;
+}
+
+int digest_walk_depth() { return kWalkDepth; }
 
 Result<void> checksum_async(const void* dev_ptr, uint64_t nbytes, uint64_t* dev_out,
                             hipStream_t stream) {

@@ -92,21 +92,75 @@ __device__ inline uint32_t lane_tile_offset(int lane) {
   return (lane & 31) * 32 + (lane >> 5) * 16;
 }
 
-__device__ inline i32x4 load_a_frag(const uint8_t* tile_base, int lane) {
-  return *reinterpret_cast<const i32x4*>(tile_base + lane_tile_offset(lane));
+// Payload bytes are always global memory: local HBM, IPC-mapped peer memory
+// or GPU-mapped host memory. Descriptors carry them as generic pointers;
+// going through address space 1 lets the compiler emit global_load/
+// global_store (one counter, in-order return, counted waits) instead of flat
+// accesses, which it may only ever wait out completely.
+template <typename T>
+using global_ptr = __attribute__((address_space(1))) T*;
+
+__device__ inline global_ptr<const uint8_t> as_global(const uint8_t* p) {
+  return (global_ptr<const uint8_t>)p;
+}
+__device__ inline global_ptr<uint8_t> as_global(uint8_t* p) {
+  return (global_ptr<uint8_t>)p;
 }
 
+// Values every lane of the wave holds alike, moved to scalar registers so
+// that what is computed and branched on from them stays scalar.
+__device__ inline uint32_t wave_uniform(uint32_t v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ inline uint64_t wave_uniform(uint64_t v) {
+  const uint32_t lo = wave_uniform(static_cast<uint32_t>(v));
+  const uint32_t hi = wave_uniform(static_cast<uint32_t>(v >> 32));
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+template <typename T>
+__device__ inline T* wave_uniform(T* p) {
+  return reinterpret_cast<T*>(wave_uniform(reinterpret_cast<uint64_t>(p)));
+}
+
+// tile_base is wave-uniform; lane_off = lane_tile_offset(lane).
+__device__ inline i32x4 load_a_frag(const uint8_t* tile_base, uint32_t lane_off) {
+  return *(global_ptr<const i32x4>)(as_global(tile_base) + lane_off);
+}
+
+__device__ inline void store_a_frag(uint8_t* tile_base, uint32_t lane_off,
+                                    const i32x4& a) {
+  // nontemporal: an A/B test against a temporal (L2-filling) store was
+  // within run variance end-to-end; the 1000-step soak record stands on
+  // this version
+  __builtin_nontemporal_store(
+      a, (global_ptr<i32x4>)(as_global(tile_base) + lane_off));
+}
+
+// The tail tile: bytes at and past nbytes read as zero ...
 __device__ inline i32x4 load_a_frag_guarded(const uint8_t* base, uint64_t tile_off,
-                                            uint64_t nbytes, int lane) {
+                                            uint64_t nbytes, uint32_t lane_off) {
   union {
     int8_t b[16];
     i32x4 v;
   } u;
-  const uint64_t lane_off = tile_off + lane_tile_offset(lane);
+  const global_ptr<const uint8_t> g = as_global(base);
+  const uint64_t off = tile_off + lane_off;
 #pragma unroll
   for (int j = 0; j < 16; ++j)
-    u.b[j] = (lane_off + j < nbytes) ? static_cast<int8_t>(base[lane_off + j]) : 0;
+    u.b[j] = (off + j < nbytes) ? static_cast<int8_t>(g[off + j]) : 0;
   return u.v;
+}
+
+// ... and are not written.
+__device__ inline void store_a_frag_guarded(uint8_t* base, uint64_t tile_off,
+                                            uint64_t nbytes, uint32_t lane_off,
+                                            const i32x4& a) {
+  const global_ptr<uint8_t> g = as_global(base);
+  const uint64_t off = tile_off + lane_off;
+  const int8_t* ab = reinterpret_cast<const int8_t*>(&a);
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    if (off + j < nbytes) g[off + j] = static_cast<uint8_t>(ab[j]);
 }
 
 __device__ inline uint64_t wave_sum_u64(uint64_t v) {
@@ -116,12 +170,16 @@ __device__ inline uint64_t wave_sum_u64(uint64_t v) {
   return v;
 }
 
+// The tile's projection A_t × B: one MFMA.
+__device__ inline i32x16 project_tile(const i32x4& a_frag, const i32x4& b_frag) {
+  const i32x16 zero = {};
+  return __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, zero, 0, 0, 0);
+}
+
 // One MFMA and one group fold: everything of a tile's hash but its position.
 __device__ inline uint64_t fold_tile_frag(const i32x4& a_frag,
                                           const i32x4& b_frag, const WReg& wr) {
-  i32x16 acc = {};
-  acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, acc, 0, 0, 0);
-  return fold_group(acc, wr);
+  return fold_group(project_tile(a_frag, b_frag), wr);
 }
 
 __device__ inline uint64_t hash_tile_frag(const i32x4& a_frag,
@@ -130,33 +188,50 @@ __device__ inline uint64_t hash_tile_frag(const i32x4& a_frag,
   return mix_slot(fold_tile_frag(a_frag, b_frag, wr), slot);
 }
 
+// Full tiles whose loads a copying wave keeps in flight while it folds the
+// current one. Measured at 1..4 on the 512 × 1 MiB put
+// (profiles/walk_pipeline_checks.md).
+constexpr int kWalkDepth = 4;
+
+// Longest run of full tiles the walk takes in one go (1 TiB).
+constexpr uint32_t kMaxRun = 1u << 30;
+
 // The batched tile walk. One desc = one contiguous run of bytes that starts
 // on a tile boundary: a whole object at object-offset 0 (CopyDesc), or a
 // segment of a striped object (StripeSeg). tile_prefix[i] is the global index
 // of desc i's first 1-KiB tile. Each wave owns a CONTIGUOUS range of global
 // tiles, so desc switches (a 64-lane reduction + one atomic) happen only at
 // desc boundaries inside the range; the current descriptor/boundary live in
-// registers (a per-tile global load of descs[]/tile_prefix[] serializes on
-// L2 latency). Every tile is loaded once with the MFMA A-fragment lane map
-// (fully coalesced) and hashed in registers; out[i] accumulates desc i's
-// partial sums and is finalized by a follow-up kernel.
+// scalar registers (a per-tile global load of descs[]/tile_prefix[]
+// serializes on L2 latency), and the range is cut into runs of full tiles of
+// one desc plus at most one tail tile per desc. Every tile is loaded once
+// with the MFMA A-fragment lane map (fully coalesced) and hashed in
+// registers; out[i] accumulates desc i's partial sums and is finalized by a
+// follow-up kernel.
 //   kCopy:     also store the fragment to dst with the same lane map.
-//   kPrefetch: software pipeline — the NEXT full tile's fragment loads while
-//              the current one is stored+hashed, so the VALU fold hides the
-//              load latency.
+//   kDepth:    software pipeline over a run of full tiles — a tile is stored
+//              and handed to the MFMA, its slot is refilled with the tile
+//              kDepth ahead, then comes the long VALU fold with kDepth loads
+//              outstanding. The steady loop waits with a counted vmcnt
+//              (2*kDepth-2 loads and stores stay in flight), never for
+//              everything. Loads never reach past the run, so nothing is
+//              read beyond a desc's last full tile. 0: load, then fold (the
+//              walk without the store is VALU-bound).
 //   StripeSeg: the tile's group fold feeds two sums — out[i], slots counted
 //              from the segment's start, and obj_out[seg.obj], slots counted
 //              from the object's start (all 64-bit). A segment at tile 0 of
 //              its object has the same slots in both, so it runs one mix per
 //              tile and adds its one sum to both accumulators.
-template <bool kCopy, bool kPrefetch, typename Desc>
+template <bool kCopy, int kDepth, typename Desc>
 __device__ __forceinline__ void digest_walk(
     const Desc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
     uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out,
     unsigned long long* __restrict__ obj_out = nullptr) {
   constexpr bool kStripe = std::is_same_v<Desc, StripeSeg>;
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // the wave index and all that follows from it: ranges, boundaries and the
+  // descriptor are the same in every lane, and the compiler is told so
+  const uint32_t wave = wave_uniform(threadIdx.x >> 6);
   const uint64_t gwave =
       static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
   const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
@@ -169,86 +244,139 @@ __device__ __forceinline__ void digest_walk(
   const WReg wr = make_w_reg(lane);
   const uint32_t lane_off = lane_tile_offset(lane);
 
-  uint32_t oi = find_seg(tile_prefix, nobjs, begin);
+  uint32_t oi = wave_uniform(find_seg(tile_prefix, nobjs, begin));
   const uint8_t* src;
   uint8_t* dst;
   uint64_t nbytes, cur_full;
   [[maybe_unused]] uint64_t first_slot = 0;  // StripeSeg: first_tile * 64
   [[maybe_unused]] uint32_t obj = 0;
+  uint64_t base_tile, next_boundary;
   auto enter_object = [&] {
     const Desc d = descs[oi];
-    src = static_cast<const uint8_t*>(d.src);
-    dst = static_cast<uint8_t*>(d.dst);
-    nbytes = d.nbytes;
+    src = wave_uniform(static_cast<const uint8_t*>(d.src));
+    dst = wave_uniform(static_cast<uint8_t*>(d.dst));
+    nbytes = wave_uniform(d.nbytes);
     cur_full = nbytes / kTileBytes;
     if constexpr (kStripe) {
-      first_slot = d.first_tile * 64;
-      obj = d.obj;
+      first_slot = wave_uniform(d.first_tile) * 64;
+      obj = wave_uniform(d.obj);
     }
+    next_boundary =
+        (oi + 1 < nobjs) ? wave_uniform(tile_prefix[oi + 1]) : ~0ull;
   };
   enter_object();
-  uint64_t base_tile = tile_prefix[oi];
-  uint64_t next_boundary = (oi + 1 < nobjs) ? tile_prefix[oi + 1] : ~0ull;
+  base_tile = wave_uniform(tile_prefix[oi]);
 
   uint64_t h = 0;
   [[maybe_unused]] uint64_t ho = 0;  // StripeSeg: the object-slot sum
   // StripeSeg, leaving a segment after h was reduced: the object's share
   [[maybe_unused]] auto flush_object = [&] {
-    if (first_slot != 0) ho = wave_sum_u64(ho);  // wave-uniform
+    if (first_slot != 0) ho = wave_sum_u64(ho);
     else ho = h;
     if (lane == 0 && ho != 0) atomicAdd(&obj_out[obj], ho);
     ho = 0;
   };
-  bool have_pre = false;
-  i32x4 pre{};
-  for (uint64_t gt = begin; gt < end; ++gt) {
+  // tile t of the current desc, projected: the VALU part of its hash
+  auto fold = [&](const i32x16& acc, uint64_t t) {
+    const uint64_t f = fold_group(acc, wr);
+    const uint64_t slot = t * 64 + lane;
+    h += mix_slot(f, slot);
+    if constexpr (kStripe)
+      if (first_slot != 0) ho += mix_slot(f, first_slot + slot);
+  };
+  // n >= 1 full tiles of the current desc, from its tile t0. Counting inside
+  // a run is 32-bit: scalar compares, where 64-bit ones take the VALU.
+  auto full_run = [&](uint64_t t0, uint32_t n) {
+    const uint8_t* s = src + t0 * kTileBytes;
+    // the fragment's last uses: the store and the MFMA
+    auto consume = [&](const i32x4& a, uint32_t i) {
+      if constexpr (kCopy)
+        store_a_frag(dst + (t0 + i) * kTileBytes, lane_off, a);
+      return project_tile(a, b_frag);
+    };
+    // tiles [i, stop) of the run one by one: load, consume, fold
+    auto plain = [&](uint32_t i, uint32_t stop) {
+      for (; i < stop; ++i)
+        fold(consume(load_a_frag(s + uint64_t{i} * kTileBytes, lane_off), i),
+             t0 + i);
+    };
+    // the walk without a pipeline, or a run too short for one
+    if (kDepth == 0 || n < 2u * kDepth) {
+      plain(0, n);
+      return;
+    }
+    if constexpr (kDepth > 0) {
+      // buf[k] holds tile i+k, then tile i+k+kDepth: the slots rotate by
+      // unrolling, no fragment is ever moved between registers.
+      i32x4 buf[kDepth];
+      // One step: consume tile i+k, refill its slot kDepth tiles ahead, then
+      // the long fold. The scheduling barriers keep that order. A load
+      // hoisted above the consumption needs a second register set, and the
+      // copy back into the slot waits for the load it was meant to leave in
+      // flight; loads issued in another order than their slots are used
+      // make the counted wait of the first slot a full one.
+      auto step = [&](uint32_t k, uint32_t i, bool refill) {
+        const i32x16 acc = consume(buf[k], i + k);
+        __builtin_amdgcn_sched_barrier(0);
+        if (refill)
+          buf[k] = load_a_frag(s + uint64_t{i + k + kDepth} * kTileBytes,
+                               lane_off);
+        __builtin_amdgcn_sched_barrier(0);
+        fold(acc, t0 + i + k);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+#pragma unroll
+      for (uint32_t k = 0; k < kDepth; ++k) {
+        buf[k] = load_a_frag(s + uint64_t{k} * kTileBytes, lane_off);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // Steady state: every step issues one load. The first group stands in
+      // front of the loop so that the loop is entered with the same loads
+      // and stores in flight as its back edge brings, and its waits count
+      // for the steady state, not for the prologue.
+      uint32_t i = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+      for (i = kDepth; i + 2u * kDepth <= n; i += kDepth) {
+#pragma unroll
+        for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+      }
+      // kDepth <= n - i < 2*kDepth tiles left: drain the slots, and the
+      // fewer than kDepth tiles behind them go one by one
+#pragma unroll
+      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, false);
+      plain(i + kDepth, n);
+    }
+  };
+
+  uint64_t gt = begin;
+  while (gt < end) {
     while (gt >= next_boundary) {
       h = wave_sum_u64(h);
       if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
       if constexpr (kStripe) flush_object();
       h = 0;
       ++oi;
-      enter_object();
       base_tile = next_boundary;
-      next_boundary = (oi + 1 < nobjs) ? tile_prefix[oi + 1] : ~0ull;
-      have_pre = false;  // prefetch belonged to the previous object
+      enter_object();
     }
     const uint64_t t = gt - base_tile;
-    const uint64_t toff = t * kTileBytes;
-    i32x4 a;
-    if (t < cur_full) {
-      if constexpr (kPrefetch) {
-        a = have_pre ? pre : load_a_frag(src + toff, lane);
-        have_pre = (gt + 1 < end) && (gt + 1 < next_boundary) &&
-                   (t + 1 < cur_full);
-        if (have_pre) pre = load_a_frag(src + toff + kTileBytes, lane);
-      } else {
-        a = load_a_frag(src + toff, lane);
-      }
-      // nontemporal: an A/B test against a temporal (L2-filling) store was
-      // within run variance end-to-end; the 1000-step soak record stands on
-      // this version
-      if constexpr (kCopy)
-        __builtin_nontemporal_store(
-            a, reinterpret_cast<i32x4*>(dst + toff + lane_off));
+    // the desc's tiles inside this wave's range, and the full ones of them
+    const uint64_t stop =
+        (end < next_boundary ? end : next_boundary) - base_tile;
+    const uint64_t full_stop = stop < cur_full ? stop : cur_full;
+    if (t < full_stop) {
+      const uint64_t left = full_stop - t;
+      const uint32_t n = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
+      full_run(t, n);
+      gt += n;
     } else {
       // tail tile: zero-padded hash, byte-guarded store
-      a = load_a_frag_guarded(src, toff, nbytes, lane);
-      if constexpr (kCopy) {
-        const uint64_t base = toff + lane_off;
-        const int8_t* ab = reinterpret_cast<const int8_t*>(&a);
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (base + j < nbytes) dst[base + j] = static_cast<uint8_t>(ab[j]);
-      }
-    }
-    const uint64_t slot = t * 64 + lane;
-    if constexpr (kStripe) {
-      const uint64_t f = fold_tile_frag(a, b_frag, wr);
-      h += mix_slot(f, slot);
-      if (first_slot != 0) ho += mix_slot(f, first_slot + slot);  // wave-uniform
-    } else {
-      h += hash_tile_frag(a, b_frag, wr, slot);
+      const uint64_t toff = t * kTileBytes;
+      const i32x4 a = load_a_frag_guarded(src, toff, nbytes, lane_off);
+      if constexpr (kCopy) store_a_frag_guarded(dst, toff, nbytes, lane_off, a);
+      fold(project_tile(a, b_frag), t);
+      ++gt;
     }
   }
   h = wave_sum_u64(h);

@@ -43,8 +43,12 @@ batched_copy_kernel(const CopyDesc* __restrict__ segs,
     const CopyDesc s = segs[si];
     const uint64_t off = (c - chunk_prefix[si]) * kChunk;
     const uint64_t len = min(kChunk, s.nbytes - off);
-    const uint8_t* src = static_cast<const uint8_t*>(s.src) + off;
-    uint8_t* dst = static_cast<uint8_t*>(s.dst) + off;
+    // global address space (digest_device.hip.h): global_load/global_store,
+    // not flat accesses
+    const dev::global_ptr<const uint8_t> src =
+        dev::as_global(static_cast<const uint8_t*>(s.src) + off);
+    const dev::global_ptr<uint8_t> dst =
+        dev::as_global(static_cast<uint8_t*>(s.dst) + off);
 
     const bool aligned = ((reinterpret_cast<uintptr_t>(src) |
                            reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
@@ -53,8 +57,8 @@ batched_copy_kernel(const CopyDesc* __restrict__ segs,
       // streamed bytes are never re-read from cache by this kernel
       uint64_t nvec = len >> 4;
       for (uint64_t i = lane; i < nvec; i += 64) {
-        v16 v = __builtin_nontemporal_load(reinterpret_cast<const v16*>(src) + i);
-        __builtin_nontemporal_store(v, reinterpret_cast<v16*>(dst) + i);
+        v16 v = __builtin_nontemporal_load((dev::global_ptr<const v16>)src + i);
+        __builtin_nontemporal_store(v, (dev::global_ptr<v16>)dst + i);
       }
       // tail bytes
       for (uint64_t i = (nvec << 4) + lane; i < len; i += 64) dst[i] = src[i];

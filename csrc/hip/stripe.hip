@@ -48,7 +48,8 @@ fused_stripe_kernel(const StripeSeg* __restrict__ segs,
                     const uint64_t* __restrict__ tile_prefix, uint32_t nseg,
                     uint64_t total_tiles, unsigned long long* __restrict__ seg_acc,
                     unsigned long long* __restrict__ obj_acc) {
-  digest_walk<true, true>(segs, tile_prefix, nseg, total_tiles, seg_acc, obj_acc);
+  digest_walk<true, kWalkDepth>(segs, tile_prefix, nseg, total_tiles, seg_acc,
+                                obj_acc);
 }
 
 // acc = {seg_acc[nseg] | obj_acc[nobj]}: each sum finalized with the length

@@ -47,6 +47,15 @@ uint64_t checksum_cpu_tiles(const void* chunk, uint64_t nbytes,
                             uint64_t first_tile);
 uint64_t checksum_cpu_finalize(uint64_t h, uint64_t object_nbytes);
 
+// Waves the batched digest/fused kernels launch for a batch of total_tiles
+// 1-KiB tiles; each owns one contiguous range of ceil(total_tiles / waves)
+// tiles. And the depth of the copying kernels' load pipeline: a run of full
+// tiles enters its steady loop from 3 * depth tiles on. Both exist only so
+// that tests can size a batch against the kernels as built; nothing else
+// should depend on them.
+uint64_t digest_grid_waves(uint64_t total_tiles);
+int digest_walk_depth();
+
 // Batched digest: one launch hashes n device buffers; out_digests is a HOST
 // array of n results (call blocks on `stream`).
 Result<void> checksum_batch(const void* const* dev_ptrs, const uint64_t* sizes,
