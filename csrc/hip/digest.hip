@@ -68,8 +68,8 @@ bbhash64_kernel(const uint8_t* __restrict__ data, uint64_t nbytes,
       static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
 
-  const i32x4 b_frag = make_b_frag(lane);
-  const WReg wr = make_w_reg(lane);
+  const i32x4 b_frag = load_b_frag(lane);
+  const WReg wr = load_w_reg(lane);
   const uint32_t lane_off = lane_tile_offset(lane);
   uint64_t h = 0;
 

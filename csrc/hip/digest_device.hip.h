@@ -33,33 +33,68 @@ __device__ inline uint32_t find_seg(const uint64_t* __restrict__ prefix,
   return lo;
 }
 
-// Per-lane B fragment: 16 bytes B[k][c] with c = lane&31, k = (lane>>5)*16+j.
-__device__ inline i32x4 make_b_frag(int lane) {
-  union {
-    int8_t b[16];
-    i32x4 v;
-  } u;
-  const int c = lane & 31;
-  const int k0 = (lane >> 5) * 16;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) u.b[j] = b_matrix(k0 + j, c);
-  return u.v;
-}
-
-// Each lane folds a FIXED set of 16 (row,col) positions; weights precomputed
-// into registers once.
+// Each lane folds a FIXED set of 16 (row,col) positions with weights it keeps
+// in registers.
 struct WReg {
   uint32_t w[16];
 };
 
-__device__ inline WReg make_w_reg(int lane) {
+// What a lane needs of the spec's two constant matrices, lane-major, built at
+// compile time: a wave fetches its constants with five 16-byte loads per lane
+// where hashing them costs it 32 splitmix64 per lane (some 480 vector
+// instructions) before its first payload load.
+//   b[lane]: the MFMA B fragment, B[k][c] with c = lane&31, k = (lane>>5)*16+j
+//   w[lane]: the fold weights W[row*32+col] of the lane's 16 accumulators in
+//            the MFMA C layout: col = lane&31, row = (j&3)+8*(j>>2)+4*(lane>>5)
+struct LaneTables {
+  alignas(16) int8_t b[64][16];
+  alignas(16) uint32_t w[64][16];
+};
+
+constexpr LaneTables make_lane_tables() {
+  LaneTables t{};
+  for (int lane = 0; lane < 64; ++lane) {
+    const int col = lane & 31;
+    const int k0 = (lane >> 5) * 16;
+    const int rbase = 4 * (lane >> 5);
+    for (int j = 0; j < 16; ++j) {
+      const int row = (j & 3) + 8 * (j >> 2) + rbase;
+      t.b[lane][j] = b_matrix(k0 + j, col);
+      t.w[lane][j] = w_weight(row * 32 + col);
+    }
+  }
+  return t;
+}
+
+// The C-layout map above against the spec's own fold groups: lane g folds
+// group g, element j.
+constexpr bool lane_tables_match_spec(const LaneTables& t) {
+  for (int g = 0; g < 64; ++g)
+    for (int j = 0; j < 16; ++j) {
+      if (t.w[g][j] != w_weight(fold_row(g, j) * 32 + fold_col(g))) return false;
+      if (t.b[g][j] != b_matrix((g >> 5) * 16 + j, fold_col(g))) return false;
+    }
+  return true;
+}
+
+inline constexpr LaneTables kLaneTablesImage = make_lane_tables();
+static_assert(lane_tables_match_spec(kLaneTablesImage));
+static_assert(sizeof(LaneTables) == 64 * 16 + 64 * 64);
+
+static __device__ const LaneTables kLaneTables = kLaneTablesImage;
+
+__device__ inline i32x4 load_b_frag(int lane) {
+  return *reinterpret_cast<const i32x4*>(kLaneTables.b[lane]);
+}
+
+__device__ inline WReg load_w_reg(int lane) {
   WReg r;
-  const int col = lane & 31;
-  const int rbase = 4 * (lane >> 5);
+  const i32x4* row = reinterpret_cast<const i32x4*>(kLaneTables.w[lane]);
 #pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int row = (j & 3) + 8 * (j >> 2) + rbase;
-    r.w[j] = w_weight(row * 32 + col);
+  for (int q = 0; q < 4; ++q) {
+    const i32x4 v = row[q];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r.w[4 * q + k] = static_cast<uint32_t>(v[k]);
   }
   return r;
 }
@@ -122,9 +157,14 @@ __device__ inline T* wave_uniform(T* p) {
   return reinterpret_cast<T*>(wave_uniform(reinterpret_cast<uint64_t>(p)));
 }
 
-// tile_base is wave-uniform; lane_off = lane_tile_offset(lane).
+// tile_base is wave-uniform; lane_off = lane_tile_offset(lane). kNt: the
+// load is nontemporal, as the copy's stores are: a copied tile is not read
+// again.
+template <bool kNt = false>
 __device__ inline i32x4 load_a_frag(const uint8_t* tile_base, uint32_t lane_off) {
-  return *(global_ptr<const i32x4>)(as_global(tile_base) + lane_off);
+  const auto p = (global_ptr<const i32x4>)(as_global(tile_base) + lane_off);
+  if constexpr (kNt) return __builtin_nontemporal_load(p);
+  else return *p;
 }
 
 __device__ inline void store_a_frag(uint8_t* tile_base, uint32_t lane_off,
@@ -222,7 +262,11 @@ constexpr uint32_t kMaxRun = 1u << 30;
 //              from the object's start (all 64-bit). A segment at tile 0 of
 //              its object has the same slots in both, so it runs one mix per
 //              tile and adds its one sum to both accumulators.
-template <bool kCopy, int kDepth, typename Desc>
+//   kNtLoads:  full tiles are loaded nontemporal. The copying kernels do; on
+//              the 512 × 1 MiB put it is worth 3–5 % of the launch
+//              (profiles/walk_persistent_checks.md). The hash-only walk was
+//              not measured with it and loads plainly.
+template <bool kCopy, int kDepth, typename Desc, bool kNtLoads = kCopy>
 __device__ __forceinline__ void digest_walk(
     const Desc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
     uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out,
@@ -240,8 +284,8 @@ __device__ __forceinline__ void digest_walk(
   const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
   if (begin >= total_tiles) return;
 
-  const i32x4 b_frag = make_b_frag(lane);
-  const WReg wr = make_w_reg(lane);
+  const i32x4 b_frag = load_b_frag(lane);
+  const WReg wr = load_w_reg(lane);
   const uint32_t lane_off = lane_tile_offset(lane);
 
   uint32_t oi = wave_uniform(find_seg(tile_prefix, nobjs, begin));
@@ -297,7 +341,9 @@ __device__ __forceinline__ void digest_walk(
     // tiles [i, stop) of the run one by one: load, consume, fold
     auto plain = [&](uint32_t i, uint32_t stop) {
       for (; i < stop; ++i)
-        fold(consume(load_a_frag(s + uint64_t{i} * kTileBytes, lane_off), i),
+        fold(consume(load_a_frag<kNtLoads>(s + uint64_t{i} * kTileBytes,
+                                           lane_off),
+                     i),
              t0 + i);
     };
     // the walk without a pipeline, or a run too short for one
@@ -319,15 +365,15 @@ __device__ __forceinline__ void digest_walk(
         const i32x16 acc = consume(buf[k], i + k);
         __builtin_amdgcn_sched_barrier(0);
         if (refill)
-          buf[k] = load_a_frag(s + uint64_t{i + k + kDepth} * kTileBytes,
-                               lane_off);
+          buf[k] = load_a_frag<kNtLoads>(
+              s + uint64_t{i + k + kDepth} * kTileBytes, lane_off);
         __builtin_amdgcn_sched_barrier(0);
         fold(acc, t0 + i + k);
         __builtin_amdgcn_sched_barrier(0);
       };
 #pragma unroll
       for (uint32_t k = 0; k < kDepth; ++k) {
-        buf[k] = load_a_frag(s + uint64_t{k} * kTileBytes, lane_off);
+        buf[k] = load_a_frag<kNtLoads>(s + uint64_t{k} * kTileBytes, lane_off);
         __builtin_amdgcn_sched_barrier(0);
       }
       // Steady state: every step issues one load. The first group stands in

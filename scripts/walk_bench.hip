@@ -1,23 +1,29 @@
-// Stand-alone timing of the copying tile walk (digest_device.hip.h) on the
-// flagship shape, 512 x 1 MiB: every pipeline depth 0..4 at several grid
-// sizes, one launch at a time (one event pair per launch) and with two
-// streams launching at once, as the two benchmark lanes do. Each variant's
-// digests and destination bytes are checked against the source. Behind
-// sections 2 of profiles/walk_pipeline_checks.md.
+// Stand-alone timing of the copying tile walk (digest_device.hip.h) on 1 MiB
+// objects: a size sweep 32..512 MiB (the flagship is 512 x 1 MiB) of the walk
+// with plain and with nontemporal payload loads, one launch at a time (one
+// event pair per launch) and with two streams launching at once, as the two
+// benchmark lanes do. Every line's digests are compared with the first line
+// of that size, and at 512 MiB the destination bytes with the source. Behind
+// profiles/walk_persistent_checks.md. (The sweeps over pipeline depth and
+// grid size behind profiles/walk_pipeline_checks.md were run with this file
+// as it stood at that change.)
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -Icsrc/include -Icsrc/hip \
 //     scripts/walk_bench.hip -o walk_bench && ./walk_bench 50
 //
-// -DPARENT with the include paths of a checkout from before the pipeline
-// (digest_walk<kCopy, kPrefetch>) times that walk with the same program.
+// -DPARENT with the include paths of a checkout from before the lane tables
+// (constants hashed by every wave, plain loads) times that walk with the
+// same program.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 
+#include "batch_launch.hip.h"
 #include "digest_device.hip.h"
 
 using namespace blackbird::gpu;
@@ -34,18 +40,17 @@ using namespace blackbird::gpu::dev;
   } while (0)
 
 #ifdef PARENT
-template <bool P>
 __global__ void __launch_bounds__(kBlock)
-walk_kernel(const CopyDesc* d, const uint64_t* p, uint32_t n, uint64_t t,
+walk_parent(const CopyDesc* d, const uint64_t* p, uint32_t n, uint64_t t,
             unsigned long long* out) {
-  digest_walk<true, P>(d, p, n, t, out);
+  digest_walk<true, kWalkDepth>(d, p, n, t, out);
 }
 #else
-template <int K>
+template <bool kNt>
 __global__ void __launch_bounds__(kBlock)
 walk_kernel(const CopyDesc* d, const uint64_t* p, uint32_t n, uint64_t t,
             unsigned long long* out) {
-  digest_walk<true, K>(d, p, n, t, out);
+  digest_walk<true, kWalkDepth, CopyDesc, kNt>(d, p, n, t, out);
 }
 #endif
 
@@ -67,9 +72,8 @@ struct Lane {
   hipStream_t stream;
 };
 
-constexpr uint32_t kN = 512;
+constexpr uint32_t kN = 512;  // objects allocated; a sweep point takes the first n
 constexpr uint64_t kS = 1 << 20;
-constexpr uint64_t kTiles = kN * kS / 1024;
 
 static void make_lane(Lane& L, uint64_t seed) {
   CK(hipMalloc(&L.src, kN * kS));
@@ -91,10 +95,12 @@ static void make_lane(Lane& L, uint64_t seed) {
   CK(hipDeviceSynchronize());
 }
 
-static void launch(KernelFn fn, int grid, const Lane& L) {
-  CK(hipMemsetAsync(L.d_out, 0, kN * sizeof(uint64_t), L.stream));
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), 0, L.stream, L.d_descs,
-                     L.d_prefix, kN, kTiles, L.d_out);
+// the first n objects, launched as enqueue_digest launches them
+static void launch(KernelFn fn, uint32_t n, const Lane& L) {
+  const uint64_t tiles = n * (kS / 1024);
+  CK(hipMemsetAsync(L.d_out, 0, n * sizeof(uint64_t), L.stream));
+  hipLaunchKernelGGL(fn, dim3(digest_grid(tiles)), dim3(kBlock), 0, L.stream,
+                     L.d_descs, L.d_prefix, n, tiles, L.d_out);
   CK(hipGetLastError());
 }
 
@@ -109,46 +115,47 @@ int main(int argc, char** argv) {
     KernelFn fn;
   };
 #ifdef PARENT
-  std::vector<Var> vars = {{"parent_prefetch", walk_kernel<true>},
-                           {"parent_noprefetch", walk_kernel<false>}};
+  std::vector<Var> vars = {{"parent", walk_parent}};
 #else
-  std::vector<Var> vars = {{"K0", walk_kernel<0>}, {"K1", walk_kernel<1>},
-                           {"K2", walk_kernel<2>}, {"K3", walk_kernel<3>},
-                           {"K4", walk_kernel<4>}};
+  std::vector<Var> vars = {{"tables", walk_kernel<false>},
+                           {"tables+nt", walk_kernel<true>}};
 #endif
-  const int grids[] = {4096, 2560, 2048, 1280, 1024, 512};
+  const uint32_t sizes_mib[] = {512, 256, 128, 64, 32};
 
   std::vector<uint8_t> h_src(kN * kS), h_dst(kN * kS);
   CK(hipMemcpy(h_src.data(), A.src, kN * kS, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> h_out(kN), ref_out;
+  std::vector<uint64_t> h_out(kN);
+  std::map<uint32_t, uint64_t> want_fold;  // per size: the first line's digests
 
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
 
   for (const Var& v : vars) {
-    for (int g : grids) {
-      // correctness: digests equal across all variants and grids, bytes equal
+    for (uint32_t n : sizes_mib) {
+      // correctness: digests equal across all lines of a size, bytes equal
       CK(hipMemsetAsync(A.dst, 0xA5, kN * kS, A.stream));
-      launch(v.fn, g, A);
+      launch(v.fn, n, A);
       CK(hipStreamSynchronize(A.stream));
-      CK(hipMemcpy(h_out.data(), A.d_out, kN * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      CK(hipMemcpy(h_out.data(), A.d_out, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
       uint64_t fold = 0;
-      for (uint64_t x : h_out) fold = fold * 0x9E3779B97F4A7C15ull + x;
-      bool bytes_ok = true;
-      if (g == 4096 || g == 1280) {
+      for (uint32_t i = 0; i < n; ++i) fold = fold * 0x9E3779B97F4A7C15ull + h_out[i];
+      if (!want_fold.count(n)) want_fold[n] = fold;
+      bool ok = fold == want_fold[n];
+      if (n == kN) {
         CK(hipMemcpy(h_dst.data(), A.dst, kN * kS, hipMemcpyDeviceToHost));
-        bytes_ok = memcmp(h_src.data(), h_dst.data(), kN * kS) == 0;
+        ok = ok && memcmp(h_src.data(), h_dst.data(), kN * kS) == 0;
       }
       // single-stream timing, one event pair per launch
-      for (int i = 0; i < 3; ++i) launch(v.fn, g, A);
+      for (int i = 0; i < 3; ++i) launch(v.fn, n, A);
       CK(hipStreamSynchronize(A.stream));
       std::vector<float> us;
       for (int i = 0; i < reps; ++i) {
-        CK(hipMemsetAsync(A.d_out, 0, kN * sizeof(uint64_t), A.stream));
+        const uint64_t tiles = n * (kS / 1024);
+        CK(hipMemsetAsync(A.d_out, 0, n * sizeof(uint64_t), A.stream));
         CK(hipEventRecord(e0, A.stream));
-        hipLaunchKernelGGL(v.fn, dim3(g), dim3(kBlock), 0, A.stream, A.d_descs,
-                           A.d_prefix, kN, kTiles, A.d_out);
+        hipLaunchKernelGGL(v.fn, dim3(digest_grid(tiles)), dim3(kBlock), 0,
+                           A.stream, A.d_descs, A.d_prefix, n, tiles, A.d_out);
         CK(hipEventRecord(e1, A.stream));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -161,8 +168,8 @@ int main(int argc, char** argv) {
       CK(hipEventRecord(e0, A.stream));
       CK(hipStreamWaitEvent(B.stream, e0, 0));
       for (int i = 0; i < reps; ++i) {
-        launch(v.fn, g, A);
-        launch(v.fn, g, B);
+        launch(v.fn, n, A);
+        launch(v.fn, n, B);
       }
       hipEvent_t eb;
       CK(hipEventCreate(&eb));
@@ -173,13 +180,13 @@ int main(int argc, char** argv) {
       float dual_ms;
       CK(hipEventElapsedTime(&dual_ms, e0, e1));
       CK(hipEventDestroy(eb));
-      printf("%-18s grid %4d  min %7.1f  med %7.1f  max %7.1f us | dual %7.1f us/launch | "
-             "digest-fold %016llx bytes %s\n",
-             v.name, g, us.front(), us[us.size() / 2], us.back(),
+      printf("%-10s %3u MiB  min %6.1f  med %6.1f  max %6.1f us"
+             " | dual %6.1f us/launch | digest-fold %016llx %s\n",
+             v.name, n, us.front(), us[us.size() / 2], us.back(),
              dual_ms * 1e3f / (2 * reps), (unsigned long long)fold,
-             bytes_ok ? "ok" : "MISMATCH");
+             ok ? "ok" : "MISMATCH");
       fflush(stdout);
-      if (!bytes_ok) return 3;
+      if (!ok) return 3;
     }
   }
   return 0;
