@@ -2,7 +2,8 @@
 // by scripts/run_tsan.sh (the reference had no sanitizer coverage at all,
 // SURVEY §5.2). Exercises the lock-heavy subsystems from many threads:
 // allocators under churn, the coordination store with watches firing during
-// mutation, and a keystone put/get/remove storm with maintenance passes.
+// mutation, a keystone put/get/remove storm with maintenance passes, and the
+// client placement cache with session bindings racing recorders and erasers.
 #include <atomic>
 #include <cstdio>
 #include <thread>
@@ -10,6 +11,7 @@
 
 #include "blackbird/allocation/pool_allocator.h"
 #include "blackbird/allocation/range_allocator.h"
+#include "blackbird/client/placement_cache.h"
 #include "blackbird/coord/coord.h"
 #include "blackbird/keystone/keystone_rpc.h"
 #include "blackbird/keystone/keystone_service.h"
@@ -285,6 +287,90 @@ void coord_repl_storm() {
   server_a.reset();
 }
 
+// Session bindings against concurrent recorders and an eraser: a digest a
+// binding reads (or finds it may refresh) is always one some recorder wrote
+// for that very key — never a freed or foreign slot. Digests are
+// (key index + 1) << 32 | counter, so the check is exact.
+void placement_cache_storm() {
+  using PC = PlacementCache;
+  constexpr uint32_t kKeys = 64;
+  PC cache;
+  cache.set_enabled(true);
+  std::vector<ObjectKey> keys;
+  for (uint32_t k = 0; k < kKeys; ++k) keys.push_back("pc" + std::to_string(k));
+  PC::KeyList all;
+  for (const auto& k : keys) all.push_back(&k);
+  auto digest_of = [](uint32_t k, uint32_t n) {
+    return (uint64_t{k} + 1) << 32 | n;
+  };
+  auto record_all = [&](uint32_t n, bool move) {
+    std::vector<PC::Put> puts;
+    for (uint32_t k = 0; k < kKeys; ++k)
+      puts.push_back({keys[k], {"pool", (move ? n : 0) * 4096ull + k, 4096,
+                                digest_of(k, n)}});
+    return puts;
+  };
+  // recorders write counters 1..400, binders 1000+t, refreshes 2000+t
+  auto written = [](uint32_t k, uint64_t d) {
+    const uint64_t n = d & 0xffffffffu;
+    return d >> 32 == k + 1 && ((n >= 1 && n <= 400) || n == 1000 ||
+                                n == 1001 || n == 2000 || n == 2001);
+  };
+  std::atomic<bool> stop{false};
+  std::atomic<uint64_t> reads{0};
+  std::vector<std::thread> ts;
+  for (int mover = 0; mover < 2; ++mover)
+    ts.emplace_back([&, mover] {
+      for (uint32_t n = 1; n <= 400; ++n)
+        cache.record(record_all(n, mover == 1 && n % 8 == 0));
+    });
+  ts.emplace_back([&] {
+    for (uint32_t n = 0; n < 400; ++n) {
+      if (n % 16 == 0) cache.erase({&keys[n % kKeys], &keys[(n + 7) % kKeys]});
+      std::this_thread::yield();
+    }
+  });
+  for (int t = 0; t < 2; ++t)
+    ts.emplace_back([&, t] {
+      std::vector<uint64_t> got(kKeys), fresh(kKeys);
+      while (!stop.load()) {
+        auto b = cache.record(record_all(1000 + t, false), &all);
+        CHECK(b.bound());
+        for (int i = 0; i < 50 && cache.read_digests(b, got.data(), kKeys); ++i) {
+          for (uint32_t k = 0; k < kKeys; ++k) {
+            CHECK(written(k, got[k]));
+            fresh[k] = digest_of(k, 2000 + t);
+          }
+          cache.refresh_digests(b, fresh.data());
+          ++reads;
+        }
+      }
+    });
+  for (size_t i = 0; i < 3; ++i) ts[i].join();
+  stop.store(true);
+  for (size_t i = 3; i < ts.size(); ++i) ts[i].join();
+  std::printf("  %llu verified digest reads\n",
+              static_cast<unsigned long long>(reads.load()));
+
+  // the size cap: one bulk record past kMaxEntries empties the cache and
+  // ends the bindings taken before it
+  auto b = cache.record(record_all(1, false), &all);
+  std::vector<uint64_t> got(kKeys);
+  CHECK(b.bound() && cache.read_digests(b, got.data(), kKeys));
+  for (uint32_t k = 0; k < kKeys; ++k) CHECK(got[k] == digest_of(k, 1));
+  std::vector<ObjectKey> many;
+  many.reserve(PC::kMaxEntries + 1);
+  for (size_t i = 0; i <= PC::kMaxEntries; ++i)
+    many.push_back("bulk" + std::to_string(i));
+  std::vector<PC::Put> bulk;
+  bulk.reserve(many.size());
+  for (const auto& k : many) bulk.push_back({k, {"pool", 0, 1, 1}});
+  cache.record(bulk);
+  CHECK(!cache.enabled_and_nonempty());
+  CHECK(!cache.valid(b));
+  CHECK(!cache.find(keys[0]));
+}
+
 }  // namespace
 
 int main() {
@@ -300,6 +386,8 @@ int main() {
   v2_replace_storm();
   std::printf("coord_repl_storm...\n");
   coord_repl_storm();
+  std::printf("placement_cache_storm...\n");
+  placement_cache_storm();
   if (failures) {
     std::printf("SELFTEST FAILED (%d checks)\n", failures);
     return 1;

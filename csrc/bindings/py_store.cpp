@@ -540,6 +540,74 @@ void bind_store(py::module_& m) {
            py::call_guard<py::gil_scoped_release>())
       .def("clear_placement_cache", &GpuClient::clear_placement_cache);
 
+  // ------------------------------------------------- placement cache
+  // (host-only logic, bound so the CPU suite can pin its invariants)
+  using PC = PlacementCache;
+  using EntryTuple = std::tuple<std::string, uint64_t, uint64_t, uint64_t>;
+  static const auto entry_tuple = [](const PC::Entry& e) {
+    return EntryTuple{e.pool_id, e.offset, e.size, e.digest};
+  };
+  static const auto key_list = [](const std::vector<std::string>& keys) {
+    PC::KeyList l;
+    for (const auto& k : keys) l.push_back(&k);
+    return l;
+  };
+  py::class_<PC::Binding>(m, "PlacementBinding")
+      .def_property_readonly("bound", &PC::Binding::bound);
+  py::class_<PC::Lookup>(m, "PlacementLookup")
+      .def_property_readonly("hits", [](const PC::Lookup& lk) {
+        std::vector<std::pair<uint32_t, EntryTuple>> out;
+        for (const auto& [i, e] : lk.hits) out.emplace_back(i, entry_tuple(e));
+        return out;
+      })
+      .def_readonly("misses", &PC::Lookup::misses);
+  py::class_<PC>(m, "PlacementCache")
+      .def(py::init<>())
+      .def("set_enabled", &PC::set_enabled)
+      .def_property_readonly("enabled", &PC::enabled)
+      .def("find", [](const PC& c, const std::string& key) {
+        auto e = c.find(key);
+        return e ? std::optional<EntryTuple>(entry_tuple(*e)) : std::nullopt;
+      })
+      // puts: (key, (pool, offset, size, digest)); returns the binding over
+      // bind_keys (unbound when none are given or one is absent)
+      .def("record", [](PC& c,
+                        const std::vector<std::pair<std::string, EntryTuple>>& puts,
+                        const std::optional<std::vector<std::string>>& bind_keys) {
+        std::vector<PC::Put> ps;
+        for (const auto& [k, e] : puts)
+          ps.push_back({k, {std::get<0>(e), std::get<1>(e), std::get<2>(e),
+                            std::get<3>(e)}});
+        if (!bind_keys) return c.record(ps);
+        const auto keys = key_list(*bind_keys);
+        return c.record(ps, &keys);
+      }, py::arg("puts"), py::arg("bind_keys") = py::none())
+      .def("erase", [](PC& c, const std::vector<std::string>& keys) {
+        c.erase(key_list(keys));
+      })
+      .def("clear", &PC::clear)
+      .def("lookup", [](PC& c,
+                        const std::vector<std::pair<std::string, uint64_t>>& wants) {
+        std::vector<PC::Want> ws;
+        for (const auto& [k, cap] : wants) ws.push_back({k, cap});
+        return c.lookup(ws);
+      })
+      .def("settle", [](PC& c, PC::Lookup& lk,
+                        const std::vector<std::string>& stale, bool bind) {
+        return c.settle(std::move(lk), key_list(stale), bind);
+      })
+      .def("digests", [](const PC& c, const PC::Binding& b)
+               -> std::optional<std::vector<uint64_t>> {
+        std::vector<uint64_t> out(b.size());
+        if (!c.read_digests(b, out.data(), out.size())) return std::nullopt;
+        return out;
+      })
+      .def("refresh", [](PC& c, const PC::Binding& b,
+                         const std::vector<uint64_t>& digests) {
+        return digests.size() == b.size() &&
+               c.refresh_digests(b, digests.data());
+      });
+
   // ------------------------------------------------------- rccl engine
   py::class_<RcclEngine>(m, "RcclEngine")
       .def(py::init<>())

@@ -643,33 +643,32 @@ Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
 // Pool-table responses with fixed-width placements: the client resolves each
 // POOL once (not each object) and decodes with zero per-item allocations.
 
-template <typename Sess>
-Result<void> GpuClient::session_kernel(Sess* sess, uint64_t* digests) {
+Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests) {
   static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
-  if (!no_graph && !sess->plan && !sess->plan_failed) {
+  if (!no_graph && !sess.plan && !sess.plan_failed) {
     auto plan = std::make_shared<gpu::FusedPutPlan>();
-    auto rb = plan->build(sess->descs.data(),
-                          static_cast<uint32_t>(sess->descs.size()), device_);
+    auto rb = plan->build(sess.descs.data(),
+                          static_cast<uint32_t>(sess.descs.size()), device_);
     if (rb.ok()) {
-      sess->plan = std::move(plan);
+      sess.plan = std::move(plan);
     } else {
-      sess->plan_failed = true;  // capture unsupported: launch path
+      sess.plan_failed = true;  // capture unsupported: launch path
       (void)hipGetLastError();   // clear any sticky launch error
       BB_LOG(WARN) << "session graph capture unavailable ("
                    << rb.error().message << "); using per-op launches";
     }
   }
-  if (sess->plan) {
-    auto r = sess->plan->run(digests);
+  if (sess.plan) {
+    auto r = sess.plan->run(digests);
     if (r.ok()) {
       session_graph_steps_.fetch_add(1);
       return r;
     }
-    sess->plan.reset();  // replay failed: fall through to launches
-    sess->plan_failed = true;
+    sess.plan.reset();  // replay failed: fall through to launches
+    sess.plan_failed = true;
   }
-  return gpu::fused_put(sess->descs.data(),
-                        static_cast<uint32_t>(sess->descs.size()), digests,
+  return gpu::fused_put(sess.descs.data(),
+                        static_cast<uint32_t>(sess.descs.size()), digests,
                         streams_[2]);
 }
 
@@ -679,15 +678,12 @@ Result<void> GpuClient::session_kernel(Sess* sess, uint64_t* digests) {
 std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
     const std::vector<DevPutItem>& items, BatchPutSession* sess) {
   const uint32_t dpi = sess ? std::max<uint32_t>(sess->descs_per_item, 1) : 1;
-  if (!sess || sess->token == 0 || sess->owner != this || items.empty() ||
-      sess->descs.size() != items.size() * dpi)
+  if (!sess || sess->token == 0 || !cache_.owns(sess->binding) ||
+      items.empty() || sess->descs.size() != items.size() * dpi)
     return std::nullopt;
-  {
-    std::lock_guard<std::mutex> g(cache_mu_);
-    if (!placement_cache_on_ || sess->cache_epoch != cache_epoch_) {
-      sess->token = 0;
-      return std::nullopt;
-    }
+  if (!cache_.valid(sess->binding)) {
+    sess->token = 0;
+    return std::nullopt;
   }
   // the session is bound to one item list: same buffers, same order
   // (dpi descs per item for replicated sessions — same src, one dst/copy)
@@ -709,7 +705,7 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
     return std::nullopt;
   }
   std::vector<uint64_t> digests(sess->descs.size(), 0);
-  auto rk = session_kernel(sess, digests.data());
+  auto rk = session_kernel(*sess, digests.data());
   if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
   // keep the session for the next step; one digest per ITEM (replicas hash
   // identical bytes; take copy 0's)
@@ -721,16 +717,9 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
     sess->token = 0;
     return std::nullopt;
   }
-  {
-    // refresh the cached digests so the verified get path accepts the new
-    // contents (raw pointers deliberately dereferenced only under the lock
-    // with the epoch re-validated)
-    std::lock_guard<std::mutex> g(cache_mu_);
-    if (sess->cache_epoch == cache_epoch_)
-      for (size_t j = 0; j < sess->entries.size(); ++j)
-        static_cast<CachedPlacement*>(sess->entries[j])->digest =
-            digests[j * dpi];
-  }
+  // refresh the cached digests so the verified get path accepts the new
+  // contents (a binding that went stale meanwhile is simply not refreshed)
+  (void)cache_.refresh_digests(sess->binding, digests.data(), dpi);
   session_put_steps_.fetch_add(1);
   return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
 }
@@ -743,7 +732,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
   // establish: a reusable session for upsert steps (token kept server-side;
   // replicated single-shard placements qualify — one desc per copy)
   const bool establish = sess != nullptr && cfg.replace && cfg.checksum &&
-                         placement_cache_on_ && fused_copy_;
+                         fused_copy_ && cache_.enabled();
   // one-shot tokens let ANY all-fused batch commit by token+digests instead
   // of re-sending every key in BATCH_PUT_COMPLETE (released at commit)
   const bool want_token = establish || (cfg.checksum && fused_copy_);
@@ -760,7 +749,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
 
   std::vector<int32_t> statuses(items.size(), 0);
   Router<true> rt(*this, fused_copy_, /*defer=*/true);
-  std::vector<std::pair<PoolId, uint64_t>> hashed_loc;  // placement cache
+  std::vector<PlacementCache::Put> cached;  // hashed items, digest filled later
 
   for (size_t i = 0; i < items.size(); ++i) {
     const wire::ItemPlaces& ip = pl.items[i];
@@ -783,7 +772,8 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
         const PoolRef& pr = pools[places[c].pool_idx];
         rt.hashed.push_back({isrc, pr.base + places[c].offset, items[i].size});
         if (c == 0)  // the verified-get cache reads copy 0
-          hashed_loc.emplace_back(pr.pool_id, places[c].offset);
+          cached.push_back({items[i].key,
+                            {pr.pool_id, places[c].offset, items[i].size, 0}});
       }
       rt.hashed_idx.push_back(static_cast<uint32_t>(i));
       continue;
@@ -826,54 +816,24 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
   if (!committed_by_token)
     BB_RETURN_IF_ERROR(complete_puts(items, rt, dpi, nullptr, statuses,
                                      /*apply_statuses=*/false));
-  if (placement_cache_on_ && !rt.hashed_idx.empty()) {
+  if (!cached.empty() && cache_.enabled()) {
     // remember our own single-copy placements + digests for RPC-free
     // verified gets (see set_placement_cache)
-    std::lock_guard<std::mutex> g(cache_mu_);
-    for (size_t j = 0; j < rt.hashed_idx.size(); ++j) {
-      const auto& it = items[rt.hashed_idx[j]];
-      if (rt.hashed_digests[j * dpi] == 0) continue;  // 0 marks "no digest"
-      CachedPlacement np{hashed_loc[j].first, hashed_loc[j].second,
-                         it.size, rt.hashed_digests[j * dpi]};
-      auto [cit, inserted] = placement_cache_.try_emplace(it.key, np);
-      if (!inserted) {
-        // overwrite with a MOVED placement (e.g. re-placed after a worker
-        // death): sessions hold descs with the old pool addresses — they
-        // must die here, or a session get would read freed/stale memory
-        if (cit->second.pool_id != np.pool_id ||
-            cit->second.offset != np.offset || cit->second.size != np.size)
-          ++cache_epoch_;
-        cit->second = np;
-      }
-    }
-    if (placement_cache_.size() > (1u << 20)) {
-      placement_cache_.clear();
-      ++cache_epoch_;
-    }
+    for (size_t j = 0; j < cached.size(); ++j)
+      cached[j].entry.digest = rt.hashed_digests[j * dpi];
     // establish the batch session when the server granted a token AND every
-    // item rode the fused single-copy path (so desc j == item j)
-    if (sess && establish && token != 0 && all_hashed) {
-      bool all_cached = true;
-      sess->descs = rt.hashed;
+    // item rode the fused single-copy path (so desc j == item j) AND every
+    // key is cached after recording
+    const bool bind = sess && establish && token != 0 && all_hashed;
+    PlacementCache::KeyList keys;
+    if (bind)
+      for (const auto& p : cached) keys.push_back(&p.key);
+    auto binding = cache_.record(cached, bind ? &keys : nullptr);
+    if (bind) {
       sess->descs_per_item = dpi;
-      sess->plan.reset();  // descs changed: a kept plan would replay stale
-      sess->plan_failed = false;
-      sess->entries.clear();
-      sess->entries.reserve(items.size());
-      for (size_t j = 0; j < items.size() && all_cached; ++j) {
-        auto cit = placement_cache_.find(items[rt.hashed_idx[j]].key);
-        if (cit == placement_cache_.end()) all_cached = false;
-        else sess->entries.push_back(&cit->second);
-      }
-      if (all_cached) {
-        sess->token = token;
-        sess->cache_epoch = cache_epoch_;
-        sess->owner = this;
-      } else {
-        sess->token = 0;
-        sess->descs.clear();
-        sess->entries.clear();
-      }
+      sess->token = binding.bound() ? token : 0;
+      if (binding.bound()) sess->rebind(rt.hashed, std::move(binding));
+      else sess->rebind({}, {});
     }
   }
   cancel_failed(items, statuses);
@@ -882,41 +842,35 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
 
 // ----------------------------------------------- verified placement cache
 
-void GpuClient::set_placement_cache(bool on) {
-  std::lock_guard<std::mutex> g(cache_mu_);
-  placement_cache_on_ = on;
-  if (!on) placement_cache_.clear();
-  ++cache_epoch_;
-}
-
 void GpuClient::invalidate(const std::vector<ObjectKey>& keys) {
-  std::lock_guard<std::mutex> g(cache_mu_);
-  for (const auto& k : keys) placement_cache_.erase(k);
-  ++cache_epoch_;
+  PlacementCache::KeyList list;
+  for (const auto& k : keys) list.push_back(&k);
+  cache_.erase(list);
 }
 
-void GpuClient::clear_placement_cache() {
-  std::lock_guard<std::mutex> g(cache_mu_);
-  placement_cache_.clear();
-  ++cache_epoch_;
+Result<void> GpuClient::refetch(const std::vector<DevGetItem>& items,
+                                const std::vector<uint32_t>& idx, bool verify,
+                                std::vector<int32_t>& statuses) {
+  std::vector<DevGetItem> sub;
+  sub.reserve(idx.size());
+  for (auto i : idx) sub.push_back(items[i]);
+  auto r = batch_get_device_rpc(sub, verify);
+  if (!r.ok()) return r.error();
+  for (size_t j = 0; j < idx.size(); ++j) statuses[idx[j]] = r.value()[j];
+  return {};
 }
 
 // Session fast path for gets: descs and want-digest slots were resolved on a
 // previous step; a step is ONE kernel launch + digest compares, zero RPCs.
 std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     const std::vector<DevGetItem>& items, BatchGetSession* sess) {
-  if (!sess || !sess->complete || sess->owner != this ||
+  if (!sess || !sess->complete || !cache_.owns(sess->binding) ||
       sess->descs.size() != items.size() || items.empty())
     return std::nullopt;
   std::vector<uint64_t> want(items.size());
-  {
-    std::lock_guard<std::mutex> g(cache_mu_);
-    if (!placement_cache_on_ || sess->cache_epoch != cache_epoch_) {
-      sess->complete = false;
-      return std::nullopt;
-    }
-    for (size_t j = 0; j < items.size(); ++j)
-      want[j] = static_cast<CachedPlacement*>(sess->entries[j])->digest;
+  if (!cache_.read_digests(sess->binding, want.data(), want.size())) {
+    sess->complete = false;
+    return std::nullopt;
   }
   for (size_t i = 0; i < items.size(); ++i)
     if (sess->descs[i].dst != items[i].ptr ||
@@ -926,7 +880,7 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     }
   BB_TRACE_SCOPE("bb::session_get");
   std::vector<uint64_t> got(items.size(), 0);
-  auto rk = session_kernel(sess, got.data());
+  auto rk = session_kernel(*sess, got.data());
   if (!rk.ok()) return {rk.error()};
   std::vector<uint32_t> miss;
   for (size_t j = 0; j < items.size(); ++j)
@@ -935,114 +889,71 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     session_get_steps_.fetch_add(1);
     return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
   }
-  // stale entries: drop them (epoch bump invalidates sessions) and refetch
-  // the misses authoritatively
-  {
-    std::lock_guard<std::mutex> g(cache_mu_);
-    for (auto j : miss) placement_cache_.erase(items[j].key);
-    ++cache_epoch_;
-  }
+  // stale entries: drop them (which ends every session on this cache) and
+  // refetch the misses authoritatively
+  PlacementCache::KeyList stale;
+  for (auto j : miss) stale.push_back(&items[j].key);
+  cache_.erase(stale);
   sess->complete = false;
   std::vector<int32_t> statuses(items.size(), 0);
-  std::vector<DevGetItem> sub;
-  sub.reserve(miss.size());
-  for (auto j : miss) sub.push_back(items[j]);
-  auto r = batch_get_device_rpc(sub, /*verify=*/true);
-  if (!r.ok()) return {r.error()};
-  for (size_t j = 0; j < miss.size(); ++j) statuses[miss[j]] = r.value()[j];
+  if (auto r = refetch(items, miss, /*verify=*/true, statuses); !r.ok())
+    return {r.error()};
   return {Result<std::vector<int32_t>>(std::move(statuses))};
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
     const std::vector<DevGetItem>& items, bool verify, BatchGetSession* sess) {
   if (auto fast = try_session_get(items, sess)) return std::move(*fast);
-  bool cache_on;
-  {
-    std::lock_guard<std::mutex> g(cache_mu_);
-    cache_on = placement_cache_on_ && !placement_cache_.empty();
-  }
-  if (!cache_on) return batch_get_device_rpc(items, verify);
+  if (!cache_.enabled_and_nonempty()) return batch_get_device_rpc(items, verify);
 
   // optimistic leg: one-sided reads of cached placements through the
   // copy+digest kernel; a digest mismatch (moved/replaced/evicted object)
   // demotes the key to the RPC leg and drops the cache entry
+  std::vector<PlacementCache::Want> wants;
+  wants.reserve(items.size());
+  for (const auto& it : items) wants.push_back({it.key, it.capacity});
+  auto lk = cache_.lookup(wants);
+  std::vector<uint32_t> miss_idx = lk.misses;
+  // pool resolution may RPC (view-versioned pool cache) — outside the lock
   std::vector<gpu::PutDesc> descs;
   std::vector<uint32_t> hit_idx;
   std::vector<uint64_t> want;
-  std::vector<uint32_t> miss_idx;
-  std::vector<std::pair<uint32_t, CachedPlacement>> lookups;
-  std::vector<CachedPlacement*> entry_ptrs;  // parallel to lookups
-  uint64_t epoch_at_lookup = 0;
-  {
-    std::lock_guard<std::mutex> g(cache_mu_);
-    for (size_t i = 0; i < items.size(); ++i) {
-      auto it = placement_cache_.find(items[i].key);
-      if (it != placement_cache_.end() && it->second.size <= items[i].capacity) {
-        lookups.emplace_back(static_cast<uint32_t>(i), it->second);
-        entry_ptrs.push_back(&it->second);
-      } else {
-        miss_idx.push_back(static_cast<uint32_t>(i));
-      }
-    }
-    epoch_at_lookup = cache_epoch_;
-  }
-  // pool resolution may RPC (view-versioned pool cache) — outside the lock
-  std::vector<CachedPlacement*> hit_entries;
-  for (size_t li = 0; li < lookups.size(); ++li) {
-    auto& [i, cp] = lookups[li];
+  for (const auto& [i, cp] : lk.hits) {
     uint8_t* base = resolve_pool_base(cp.pool_id);
-    const auto du = reinterpret_cast<uintptr_t>(items[i].ptr);
-    if (base &&
-        ((du | reinterpret_cast<uintptr_t>(base + cp.offset)) & 15) == 0) {
+    if (base && aligned16(items[i].ptr, base + cp.offset)) {
       descs.push_back(
           {base + cp.offset, static_cast<uint8_t*>(items[i].ptr), cp.size});
       hit_idx.push_back(i);
       want.push_back(cp.digest);
-      hit_entries.push_back(entry_ptrs[li]);
     } else {
       miss_idx.push_back(i);
     }
   }
   std::vector<int32_t> statuses(items.size(), 0);
-  bool all_verified = false;
   if (!descs.empty()) {
     BB_TRACE_SCOPE("bb::cached_get");
     std::vector<uint64_t> got(descs.size(), 0);
     auto r = gpu::fused_put(descs.data(), static_cast<uint32_t>(descs.size()),
                             got.data(), streams_[2]);
     if (!r.ok()) return r.error();
-    std::lock_guard<std::mutex> g(cache_mu_);
-    all_verified = true;
-    for (size_t j = 0; j < hit_idx.size(); ++j) {
+    PlacementCache::KeyList stale;
+    for (size_t j = 0; j < hit_idx.size(); ++j)
       if (got[j] != want[j]) {
-        placement_cache_.erase(items[hit_idx[j]].key);
-        ++cache_epoch_;
+        stale.push_back(&items[hit_idx[j]].key);
         miss_idx.push_back(hit_idx[j]);  // refetch authoritatively
-        all_verified = false;
       }
-    }
     // establish the get session when every item was a verified cache hit
     // (desc j == item j) and no concurrent thread mutated the cache
-    if (sess && all_verified && miss_idx.empty() &&
-        hit_idx.size() == items.size() && epoch_at_lookup == cache_epoch_) {
-      sess->descs = std::move(descs);
-      sess->plan.reset();
-      sess->plan_failed = false;
-      sess->entries.assign(hit_entries.begin(), hit_entries.end());
-      sess->cache_epoch = cache_epoch_;
-      sess->owner = this;
+    auto binding = cache_.settle(std::move(lk), stale,
+                                 sess && hit_idx.size() == items.size());
+    if (binding.bound()) {
+      sess->rebind(std::move(descs), std::move(binding));
       sess->complete = true;
     }
   }
   if (!miss_idx.empty()) {
     std::sort(miss_idx.begin(), miss_idx.end());
-    std::vector<DevGetItem> sub;
-    sub.reserve(miss_idx.size());
-    for (auto i : miss_idx) sub.push_back(items[i]);
-    auto r = batch_get_device_rpc(sub, verify);
-    if (!r.ok()) return r.error();
-    for (size_t j = 0; j < miss_idx.size(); ++j)
-      statuses[miss_idx[j]] = r.value()[j];
+    BB_RETURN_IF_ERROR(refetch(items, miss_idx, verify, statuses));
   }
   return statuses;
 }
@@ -1358,18 +1269,10 @@ Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
   // (covers this client's own puts), metadata RPC as the general fallback
   ShuffleResolver resolve = [this](const ObjectKey& key,
                                    uint64_t size) -> const void* {
-    bool cached = false;
-    CachedPlacement cp2;
-    {
-      std::lock_guard<std::mutex> g(cache_mu_);
-      auto it = placement_cache_.find(key);
-      if (it != placement_cache_.end() && it->second.size == size) {
-        cp2 = it->second;
-        cached = true;
-      }
-    }
-    if (cached) {  // resolve_pool_base may RPC — not under the lock
-      if (uint8_t* base = resolve_pool_base(cp2.pool_id)) return base + cp2.offset;
+    if (auto cp2 = cache_.find(key); cp2 && cp2->size == size) {
+      // resolve_pool_base may RPC — the cache lock is not held here
+      if (uint8_t* base = resolve_pool_base(cp2->pool_id))
+        return base + cp2->offset;
       return nullptr;
     }
     auto meta = c_.meta_call<KeyMsg, GetWorkersResponse>(M::GET_WORKERS,

@@ -21,6 +21,7 @@
 #include <unordered_map>
 
 #include "blackbird/client/client.h"
+#include "blackbird/client/placement_cache.h"
 #include "blackbird/client/shuffle.h"
 #include "blackbird/gpu/gpu_kernels.h"
 
@@ -63,36 +64,39 @@ class GpuClient {
   // re-validated each step. Requires replace=true, checksum=true
   // and the placement cache enabled; replicated placements are supported
   // (one destination per copy).
-  // Worker death: a re-placing put bumps the cache epoch (moved placements
-  // kill sessions holding the old pool addresses). A get-session step
+  // A session's hold on the placement cache is a PlacementCache::Binding:
+  // the cache that issued it refuses it once any placement was erased,
+  // moved or cleared, so a step never reaches a dead cache entry.
+  // Worker death: a re-placing put kills the bindings (moved placements
+  // end sessions holding the old pool addresses). A get-session step
   // BEFORE any re-put reads the dead pool one-sidedly: across processes
   // (production: dmabuf-IPC imports pin the memory) that is a digest
   // mismatch → RPC fallback; an EMBEDDED worker that frees its pool
   // in-process can fault — stop in-process workers only after their
   // clients.
-  struct BatchPutSession {
-    uint64_t token = 0;  // server put-session token (0 = not established)
-    uint64_t cache_epoch = 0;
-    void* owner = nullptr;  // GpuClient that built it (entries point into
-                            // that client's placement cache)
-    std::vector<gpu::PutDesc> descs;  // src=user buffer, dst=pool range
-    // replicated sessions carry one desc PER COPY per item (same src, one
-    // dst per replica); descs.size() == items.size() * descs_per_item
-    uint32_t descs_per_item = 1;
-    std::vector<void*> entries;       // CachedPlacement* digest slots
+  struct SessionCore {
+    PlacementCache::Binding binding;  // the items' digest slots, item order
+    std::vector<gpu::PutDesc> descs;  // user buffer ↔ pool range
     // hipGraph replay of the step (descs fixed ⇒ captured once, one graph
     // launch per step); built lazily on the first session step
     std::shared_ptr<gpu::FusedPutPlan> plan;
     bool plan_failed = false;  // capture unsupported: stay on fused_put
+    // a new desc list: a kept plan would replay the old one
+    void rebind(std::vector<gpu::PutDesc> d, PlacementCache::Binding b) {
+      descs = std::move(d);
+      binding = std::move(b);
+      plan.reset();
+      plan_failed = false;
+    }
   };
-  struct BatchGetSession {
+  struct BatchPutSession : SessionCore {  // descs: src=user, dst=pool
+    uint64_t token = 0;  // server put-session token (0 = not established)
+    // replicated sessions carry one desc PER COPY per item (same src, one
+    // dst per replica); descs.size() == items.size() * descs_per_item
+    uint32_t descs_per_item = 1;
+  };
+  struct BatchGetSession : SessionCore {  // descs: src=pool, dst=user
     bool complete = false;  // covers every item
-    uint64_t cache_epoch = 0;
-    void* owner = nullptr;
-    std::vector<gpu::PutDesc> descs;  // src=pool range, dst=user buffer
-    std::vector<void*> entries;       // CachedPlacement* want-digest slots
-    std::shared_ptr<gpu::FusedPutPlan> plan;
-    bool plan_failed = false;
   };
 
   // One metadata RPC + fused transfers + one batched checksum launch.
@@ -150,9 +154,11 @@ class GpuClient {
   // registers. Caveat: a REMOVE by another client is not observed until the
   // freed bytes are actually overwritten (content-validated staleness);
   // call invalidate()/clear_placement_cache() where that matters.
-  void set_placement_cache(bool on);
+  // The cache itself (map, lock, enabled flag, session bindings) is a
+  // PlacementCache; these forward to it.
+  void set_placement_cache(bool on) { cache_.set_enabled(on); }
   void invalidate(const std::vector<ObjectKey>& keys);
-  void clear_placement_cache();
+  void clear_placement_cache() { cache_.clear(); }
 
  private:
   // Resolve a shard to a device-visible pointer (local or IPC-mapped peer
@@ -203,6 +209,10 @@ class GpuClient {
   // the RPC leg of the v2 get (cache misses route here)
   Result<std::vector<int32_t>> batch_get_device_rpc(
       const std::vector<DevGetItem>& items, bool verify);
+  // items[idx] through the RPC leg, answers scattered into statuses
+  Result<void> refetch(const std::vector<DevGetItem>& items,
+                       const std::vector<uint32_t>& idx, bool verify,
+                       std::vector<int32_t>& statuses);
   Result<void> staged_write(const ShardPlacement& s, const void* dev_src);
   Result<void> staged_write_buf(const ShardPlacement& s, const void* dev_src,
                                 void* staging, uint64_t staging_size);
@@ -238,19 +248,7 @@ class GpuClient {
   static constexpr int kFanThreads = 8;
   std::mutex staging_pool_mu_;
   std::vector<void*> staging_pool_;  // idle pinned kFanBuf buffers
-  struct CachedPlacement {
-    PoolId pool_id;
-    uint64_t offset = 0;
-    uint64_t size = 0;
-    uint64_t digest = 0;
-  };
-  bool placement_cache_on_ = false;
-  std::mutex cache_mu_;
-  std::unordered_map<ObjectKey, CachedPlacement> placement_cache_;
-  // bumped (under cache_mu_) on every erase/clear: sessions hold raw
-  // CachedPlacement* into the map, valid only while their epoch matches
-  // (unordered_map mapped values are stable across insert/rehash)
-  uint64_t cache_epoch_ = 0;
+  PlacementCache cache_;  // own lock; sessions hold Bindings into it
   std::atomic<uint64_t> session_put_steps_{0};
   std::atomic<uint64_t> session_get_steps_{0};
   std::atomic<uint64_t> session_graph_steps_{0};
@@ -259,8 +257,7 @@ class GpuClient {
   // run the session desc list: captured-graph replay when available,
   // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
   // or a failed capture pins the session to the launch path)
-  template <typename Sess>
-  Result<void> session_kernel(Sess* sess, uint64_t* digests);
+  Result<void> session_kernel(SessionCore& sess, uint64_t* digests);
   bool fused_copy_ = true;
   bool initialized_ = false;
 };
