@@ -2,8 +2,9 @@
 // by scripts/run_tsan.sh (the reference had no sanitizer coverage at all,
 // SURVEY §5.2). Exercises the lock-heavy subsystems from many threads:
 // allocators under churn, the coordination store with watches firing during
-// mutation, a keystone put/get/remove storm with maintenance passes, and the
-// client placement cache with session bindings racing recorders and erasers.
+// mutation, a keystone put/get/remove storm with maintenance passes, the
+// client placement cache with session bindings racing recorders and erasers,
+// and the clients' batch fan-out.
 #include <atomic>
 #include <cstdio>
 #include <thread>
@@ -11,6 +12,7 @@
 
 #include "blackbird/allocation/pool_allocator.h"
 #include "blackbird/allocation/range_allocator.h"
+#include "blackbird/client/batch_util.h"
 #include "blackbird/client/placement_cache.h"
 #include "blackbird/coord/coord.h"
 #include "blackbird/keystone/keystone_rpc.h"
@@ -371,6 +373,36 @@ void placement_cache_storm() {
   CHECK(!cache.find(keys[0]));
 }
 
+// The batch fan-out from several callers at once, as pipelined batches do:
+// every index of every call runs exactly once, on at most `threads` threads,
+// and all of it is visible to the caller when the call returns.
+void fan_out_storm() {
+  std::vector<std::thread> ts;
+  for (int caller = 0; caller < 4; ++caller)
+    ts.emplace_back([caller] {
+      for (size_t n : {size_t{0}, size_t{1}, size_t{3}, size_t{257}}) {
+        const int threads = 1 + caller;
+        std::vector<int> hits(n, 0);  // plain ints: each index has one writer
+        std::vector<int> per_thread(threads, 0);
+        fan_out_threads(n, threads, [&](int t, auto& next) {
+          CHECK(t >= 0 && t < threads);
+          for (size_t i; next(i);) {
+            ++hits[i];
+            ++per_thread[t];
+          }
+        });
+        size_t total = 0;
+        for (int c : per_thread) total += c;
+        CHECK(total == n);
+        for (int h : hits) CHECK(h == 1);
+        std::vector<size_t> seen(n, SIZE_MAX);
+        fan_out(n, threads, [&](size_t i) { seen[i] = i; });
+        for (size_t i = 0; i < n; ++i) CHECK(seen[i] == i);
+      }
+    });
+  for (auto& t : ts) t.join();
+}
+
 }  // namespace
 
 int main() {
@@ -388,6 +420,8 @@ int main() {
   coord_repl_storm();
   std::printf("placement_cache_storm...\n");
   placement_cache_storm();
+  std::printf("fan_out_storm...\n");
+  fan_out_storm();
   if (failures) {
     std::printf("SELFTEST FAILED (%d checks)\n", failures);
     return 1;

@@ -5,13 +5,13 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <atomic>
 #include <cstring>
 #include <future>
 #include <thread>
 
 #include <hip/hip_runtime_api.h>
 
+#include "blackbird/client/batch_util.h"
 #include "blackbird/client/batch_wire.h"
 #include "blackbird/client/pool_mapper.h"
 #include "blackbird/common/hex.h"
@@ -204,99 +204,51 @@ Result<AccessInfo> Client::pool_access(const PoolId& id) {
 
 // ------------------------------------------------------ shard transfer
 
-Result<void> Client::write_shard(const ShardPlacement& s, const void* src) {
-  if (opts_.force_tcp) {
-    AccessInfo a2;
-    if (s.access.endpoint.empty()) {
-      auto r = pool_access(s.pool_id);
-      if (!r.ok()) return r.error();
-      a2 = std::move(r.value());
-    } else a2 = s.access;
-    auto* dc = data_client(a2.endpoint);
-    if (!dc) return Error{ErrorCode::CONNECT_FAILED, "data plane " + a2.endpoint};
+namespace {
+// The direction-specific pieces of move_shard. `pool` is the shard's address
+// in a mapped pool, `user` the caller's buffer.
+template <bool Write>
+using UserPtr = std::conditional_t<Write, const void*, void*>;
+
+template <bool Write>
+void host_copy(void* pool, UserPtr<Write> user, uint64_t n) {
+  if constexpr (Write) std::memcpy(pool, user, n);
+  else std::memcpy(user, pool, n);
+}
+
+template <bool Write>
+Result<void> device_copy(void* pool, UserPtr<Write> user, uint64_t n) {
+  if constexpr (Write)
+    return gpu::copy_sync(pool, user, n, hipMemcpyHostToDevice);
+  else
+    return gpu::copy_sync(user, pool, n, hipMemcpyDeviceToHost);
+}
+
+template <bool Write>
+Result<void> tcp_copy(rpc::RpcClient& dc, const ShardPlacement& s,
+                      UserPtr<Write> user, int timeout_ms) {
+  if constexpr (Write) {
     WriteReq req;
     req.pool_id = s.pool_id;
     req.offset = s.offset;
-    req.src = src;
+    req.src = user;
     req.len = s.length;
-    auto r = dc->call_raw(M::DATA_WRITE, serde::to_bytes(req), opts_.rpc_timeout_ms);
+    auto r = dc.call_raw(M::DATA_WRITE, serde::to_bytes(req), timeout_ms);
     if (!r.ok()) return r.error();
-    return {};
-  }
-  AccessInfo resolved;
-  if (s.access.endpoint.empty()) {
-    auto r = pool_access(s.pool_id);
-    if (!r.ok()) return r.error();
-    resolved = std::move(r.value());
-  }
-  const AccessInfo& a = s.access.endpoint.empty() ? resolved : s.access;
-  {
-    bool is_dev = false;
-    if (void* base = LocalPools::inst().lookup(s.pool_id, &is_dev)) {
-      uint8_t* dst = static_cast<uint8_t*>(base) + s.offset;
-      if (!is_dev) {
-        std::memcpy(dst, src, s.length);
-        return {};
-      }
-      if (gpu::copy_sync(dst, src, s.length, hipMemcpyHostToDevice).ok())
-        return {};
-    } else if (auto* be = LocalPools::inst().backend(s.pool_id)) {
-      // unmapped same-process pool (direct-IO NVMe tier): call the backend
-      // directly instead of framing the bytes through TCP loopback
-      return be->write(s.offset, src, s.length);
-    }
-  }
-  if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
-    // one-sided host fast path: the pool end address is not known here; map
-    // generously (offset+length) — the segment is fixed-size, mapping is
-    // cached by name with the first size seen, so map the whole pool lazily
-    // via /dev/shm stat.
-    if (void* base = mapper_->map_shm(a.shm_name, 0)) {
-      std::memcpy(static_cast<uint8_t*>(base) + s.offset, src, s.length);
-      return {};
-    }
-  }
-  if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty() &&
-      gpu::available()) {
-    if (void* base = mapper_->open_ipc(a.ipc_handle_hex, a.device_id)) {
-      auto e = gpu::copy_sync(static_cast<uint8_t*>(base) + s.offset, src,
-                              s.length, hipMemcpyHostToDevice);
-      if (e.ok()) return {};
-      BB_LOG(WARN) << "IPC write failed: " << e.error().message
-                   << " — falling back to TCP";
-    }
-  }
-  // TCP fallback
-  auto* dc = data_client(a.endpoint);
-  if (!dc) return Error{ErrorCode::CONNECT_FAILED, "data plane " + a.endpoint};
-  WriteReq req;
-  req.pool_id = s.pool_id;
-  req.offset = s.offset;
-  req.src = src;
-  req.len = s.length;
-  auto r = dc->call_raw(M::DATA_WRITE, serde::to_bytes(req), opts_.rpc_timeout_ms);
-  if (!r.ok()) return r.error();
-  return {};
-}
-
-Result<void> Client::read_shard(const ShardPlacement& s, void* dst) {
-  if (opts_.force_tcp) {
-    AccessInfo a2;
-    if (s.access.endpoint.empty()) {
-      auto r = pool_access(s.pool_id);
-      if (!r.ok()) return r.error();
-      a2 = std::move(r.value());
-    } else a2 = s.access;
-    auto* dc = data_client(a2.endpoint);
-    if (!dc) return Error{ErrorCode::CONNECT_FAILED, "data plane " + a2.endpoint};
+  } else {
     ReadReq req{s.pool_id, s.offset, s.length};
-    auto r = dc->call_raw(M::DATA_READ, serde::to_bytes(req), opts_.rpc_timeout_ms);
+    auto r = dc.call_raw(M::DATA_READ, serde::to_bytes(req), timeout_ms);
     if (!r.ok()) return r.error();
     if (r.value().size() != s.length)
       return Error{ErrorCode::SIZE_MISMATCH, "short read"};
-    std::memcpy(dst, r.value().data(), s.length);
-    return {};
+    std::memcpy(user, r.value().data(), s.length);
   }
+  return {};
+}
+}  // namespace
+
+template <bool Write>
+Result<void> Client::move_shard(const ShardPlacement& s, UserPtr<Write> user) {
   AccessInfo resolved;
   if (s.access.endpoint.empty()) {
     auto r = pool_access(s.pool_id);
@@ -304,70 +256,94 @@ Result<void> Client::read_shard(const ShardPlacement& s, void* dst) {
     resolved = std::move(r.value());
   }
   const AccessInfo& a = s.access.endpoint.empty() ? resolved : s.access;
-  {
+  if (!opts_.force_tcp) {
     bool is_dev = false;
     if (void* base = LocalPools::inst().lookup(s.pool_id, &is_dev)) {
-      uint8_t* src2 = static_cast<uint8_t*>(base) + s.offset;
+      void* pool = static_cast<uint8_t*>(base) + s.offset;
       if (!is_dev) {
-        std::memcpy(dst, src2, s.length);
+        host_copy<Write>(pool, user, s.length);
         return {};
       }
-      if (gpu::copy_sync(dst, src2, s.length, hipMemcpyDeviceToHost).ok())
-        return {};
+      // a failed device copy falls on to the later rungs
+      if (device_copy<Write>(pool, user, s.length).ok()) return {};
     } else if (auto* be = LocalPools::inst().backend(s.pool_id)) {
-      // unmapped same-process pool (direct-IO NVMe tier): read through the
-      // backend instead of TCP loopback
-      return be->read(s.offset, dst, s.length);
+      // unmapped same-process pool (direct-IO NVMe tier): call the backend
+      // directly instead of framing the bytes through TCP loopback
+      if constexpr (Write) return be->write(s.offset, user, s.length);
+      else return be->read(s.offset, user, s.length);
     }
-  }
-  if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
-    if (void* base = mapper_->map_shm(a.shm_name, 0)) {
-      std::memcpy(dst, static_cast<uint8_t*>(base) + s.offset, s.length);
-      return {};
+    if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
+      // one-sided host fast path. The pool's size is not known here: size 0
+      // maps the whole segment (sized by stat), cached by name.
+      if (void* base = mapper_->map_shm(a.shm_name, 0)) {
+        host_copy<Write>(static_cast<uint8_t*>(base) + s.offset, user,
+                         s.length);
+        return {};
+      }
     }
-  }
-  if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty() &&
-      gpu::available()) {
-    if (void* base = mapper_->open_ipc(a.ipc_handle_hex, a.device_id)) {
-      auto e = gpu::copy_sync(dst, static_cast<uint8_t*>(base) + s.offset,
-                              s.length, hipMemcpyDeviceToHost);
-      if (e.ok()) return {};
+    if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty() &&
+        gpu::available()) {
+      if (void* base = mapper_->open_ipc(a.ipc_handle_hex, a.device_id)) {
+        auto e = device_copy<Write>(static_cast<uint8_t*>(base) + s.offset,
+                                    user, s.length);
+        if (e.ok()) return {};
+        BB_LOG(WARN) << "IPC " << (Write ? "write" : "read")
+                     << " failed: " << e.error().message
+                     << " — falling back to TCP";
+      }
     }
   }
   auto* dc = data_client(a.endpoint);
   if (!dc) return Error{ErrorCode::CONNECT_FAILED, "data plane " + a.endpoint};
-  ReadReq req{s.pool_id, s.offset, s.length};
-  auto r = dc->call_raw(M::DATA_READ, serde::to_bytes(req), opts_.rpc_timeout_ms);
-  if (!r.ok()) return r.error();
-  if (r.value().size() != s.length)
-    return Error{ErrorCode::SIZE_MISMATCH, "short read"};
-  std::memcpy(dst, r.value().data(), s.length);
-  return {};
+  return tcp_copy<Write>(*dc, s, user, opts_.rpc_timeout_ms);
 }
+
+Result<void> Client::write_shard(const ShardPlacement& s, const void* src) {
+  return move_shard<true>(s, src);
+}
+
+Result<void> Client::read_shard(const ShardPlacement& s, void* dst) {
+  return move_shard<false>(s, dst);
+}
+
+namespace {
+// Every shard of `copy` with its offset in the object: body(shard, offset)
+// runs inline for one shard, on one std::async each for several. Returns the
+// per-shard results in shard order, or nullopt, with nothing run, when the
+// shard lengths do not add up to `size`.
+template <typename Body>
+std::optional<std::vector<Result<void>>> walk_copy(const CopyPlacement& copy,
+                                                   uint64_t size, Body&& body) {
+  uint64_t total = 0;
+  for (const auto& s : copy.shards) total += s.length;
+  if (total != size) return std::nullopt;
+  std::vector<Result<void>> out;
+  if (copy.shards.size() == 1) {
+    out.push_back(body(copy.shards[0], uint64_t{0}));
+    return out;
+  }
+  std::vector<std::future<Result<void>>> futs;
+  uint64_t off = 0;
+  for (const auto& s : copy.shards) {
+    futs.push_back(std::async(std::launch::async,
+                              [&body, &s, off] { return body(s, off); }));
+    off += s.length;
+  }
+  for (auto& f : futs) out.push_back(f.get());
+  return out;
+}
+}  // namespace
 
 Result<void> Client::write_copies(const std::vector<CopyPlacement>& copies,
                                   const void* data, uint64_t size) {
   for (const auto& copy : copies) {
-    // correct running source offset per shard (reference bug fixed)
-    std::vector<std::pair<const ShardPlacement*, uint64_t>> work;
-    uint64_t off = 0;
-    for (const auto& s : copy.shards) {
-      work.emplace_back(&s, off);
-      off += s.length;
-    }
-    if (off != size)
+    auto done = walk_copy(copy, size, [&](const ShardPlacement& s, uint64_t off) {
+      return write_shard(s, static_cast<const uint8_t*>(data) + off);
+    });
+    if (!done)
       return Error{ErrorCode::SIZE_MISMATCH, "placement does not cover object"};
-    if (work.size() == 1) {
-      BB_RETURN_IF_ERROR(write_shard(*work[0].first,
-                                     static_cast<const uint8_t*>(data)));
-    } else {
-      std::vector<std::future<Result<void>>> futs;
-      for (auto& [sp, o] : work)
-        futs.push_back(std::async(std::launch::async, [this, sp, o, data] {
-          return write_shard(*sp, static_cast<const uint8_t*>(data) + o);
-        }));
-      for (auto& f : futs) BB_RETURN_IF_ERROR(f.get());
-    }
+    for (auto& r : *done)
+      if (!r.ok()) return r.error();
   }
   return {};
 }
@@ -376,32 +352,16 @@ Result<void> Client::read_copy(const std::vector<CopyPlacement>& copies,
                                void* dst, uint64_t size) {
   Error last{ErrorCode::NO_PLACEMENT, "no copies"};
   for (const auto& copy : copies) {
-    uint64_t off = 0;
+    auto done = walk_copy(copy, size, [&](const ShardPlacement& s, uint64_t off) {
+      return read_shard(s, static_cast<uint8_t*>(dst) + off);
+    });
+    if (!done) continue;
     bool ok = true;
-    std::vector<std::tuple<const ShardPlacement*, uint64_t>> work;
-    for (const auto& s : copy.shards) {
-      work.emplace_back(&s, off);
-      off += s.length;
-    }
-    if (off != size) continue;
-    if (work.size() == 1) {
-      auto r = read_shard(*std::get<0>(work[0]), dst);
-      if (r.ok()) return {};
-      last = r.error();
-      continue;
-    }
-    std::vector<std::future<Result<void>>> futs;
-    for (auto& [sp, o] : work)
-      futs.push_back(std::async(std::launch::async, [this, sp = sp, o = o, dst] {
-        return read_shard(*sp, static_cast<uint8_t*>(dst) + o);
-      }));
-    for (auto& f : futs) {
-      auto r = f.get();
+    for (auto& r : *done)
       if (!r.ok()) {
         ok = false;
         last = r.error();
       }
-    }
     if (ok) return {};
   }
   return last;
@@ -608,6 +568,32 @@ void Client::cancel_puts(const std::vector<ObjectKey>& keys) {
     meta_call_raw(M::BATCH_PUT_CANCEL, serde::to_bytes(KeysMsg{keys}));
 }
 
+// ---- put epilogue of the host paths (v1 and v2) ----
+
+Result<void> Client::finish_puts(
+    const std::vector<PutItem>& items, const std::vector<uint64_t>& digests,
+    std::vector<int32_t>& statuses,
+    const std::function<std::vector<std::vector<uint64_t>>(size_t)>&
+        shard_digests_of,
+    const std::function<bool(size_t)>& cancellable) {
+  std::vector<PutCompleteRequest> completes;
+  std::vector<ObjectKey> cancels;
+  std::vector<uint32_t> complete_idx;
+  for (size_t i = 0; i < items.size(); ++i) {
+    if (statuses[i] != 0) {
+      if (cancellable(i)) cancels.push_back(items[i].key);
+      continue;
+    }
+    PutCompleteRequest pc{items[i].key, digests[i], {}};
+    if (shard_digests_of) pc.shard_digests = shard_digests_of(i);
+    completes.push_back(std::move(pc));
+    complete_idx.push_back(static_cast<uint32_t>(i));
+  }
+  BB_RETURN_IF_ERROR(complete_by_keys(completes, complete_idx, &statuses));
+  cancel_puts(cancels);
+  return {};
+}
+
 // Token fast path for the host tier: placements unchanged since the last
 // step ⇒ two tiny RPCs around direct memcpys + CPU digests. Mirrors
 // GpuClient::try_session_put, including the ordering guarantee: the server
@@ -633,23 +619,11 @@ std::optional<std::vector<int32_t>> Client::try_host_session_put(
     return std::nullopt;
   }
   std::vector<uint64_t> digests(items.size(), 0);
-  {
-    std::atomic<size_t> next{0};
-    const int nthreads = std::max(
-        1, std::min<int>(opts_.io_threads, static_cast<int>(items.size())));
-    std::vector<std::future<void>> futs;
-    for (int t = 0; t < nthreads; ++t)
-      futs.push_back(std::async(std::launch::async, [&] {
-        for (size_t i = next.fetch_add(1); i < items.size();
-             i = next.fetch_add(1)) {
-          for (uint32_t k = 0; k < dpi; ++k)
-            std::memcpy(sess->dsts[i * dpi + k], items[i].data,
-                        items[i].size);
-          digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
-        }
-      }));
-    for (auto& f : futs) f.get();
-  }
+  fan_out(items.size(), opts_.io_threads, [&](size_t i) {
+    for (uint32_t k = 0; k < dpi; ++k)
+      std::memcpy(sess->dsts[i * dpi + k], items[i].data, items[i].size);
+    digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
+  });
   auto r2 = commit_by_token(sess->token, /*release=*/false, digests.data(),
                             digests.size());
   if (!r2.ok()) {
@@ -675,22 +649,6 @@ uint8_t* Client::host_pool_base(const PoolId& id, AccessInfo* access) {
   return out;
 }
 
-namespace {
-struct HostPoolRef {
-  PoolId pool_id;
-  uint8_t* base = nullptr;
-  AccessInfo access;
-  ShardPlacement shard(uint64_t offset, uint64_t length) const {
-    ShardPlacement sp;
-    sp.pool_id = pool_id;
-    sp.offset = offset;
-    sp.length = length;
-    sp.access = access;
-    return sp;
-  }
-};
-}  // namespace
-
 // Host twin of GpuClient::batch_put_device_v2: compact request, pool-table
 // response, memcpy into mapped pools (shard RPC fallback), digests computed
 // on the fly, commit by one-shot token when the whole batch qualifies —
@@ -709,11 +667,9 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
   BB_RETURN_IF_ERROR(
       wire::decode_put_start2_response(resp.value(), items.size(), pl));
   const uint64_t token = pl.token;
-  std::vector<HostPoolRef> pools(pl.pools.size());
-  for (size_t i = 0; i < pools.size(); ++i) {
-    pools[i].pool_id = pl.pools[i];
-    pools[i].base = host_pool_base(pools[i].pool_id, &pools[i].access);
-  }
+  const auto pools = resolve_pool_table(
+      pl.pools,
+      [this](const PoolId& id, AccessInfo* a) { return host_pool_base(id, a); });
 
   std::vector<int32_t> statuses(items.size(), 0);
   for (size_t i = 0; i < items.size(); ++i) {
@@ -749,36 +705,24 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
   // transfers + digests fan out per item (digest runs while the bytes are
   // still cache-hot from the memcpy)
   std::vector<uint64_t> digests(items.size(), 0);
-  {
-    std::atomic<size_t> next{0};
-    const int nthreads = std::max(
-        1, std::min<int>(opts_.io_threads, static_cast<int>(items.size())));
-    std::vector<std::future<void>> futs;
-    for (int t = 0; t < nthreads; ++t)
-      futs.push_back(std::async(std::launch::async, [&] {
-        for (size_t i = next.fetch_add(1); i < items.size();
-             i = next.fetch_add(1)) {
-          if (statuses[i] != 0) continue;
-          for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
-            const wire::Place& p = pl.places_of(pl.items[i])[c];
-            HostPoolRef& pr = pools[p.pool_idx];
-            if (pr.base) {
-              std::memcpy(pr.base + p.offset, items[i].data, items[i].size);
-            } else {
-              auto r = write_shard(pr.shard(p.offset, items[i].size),
-                                   items[i].data);
-              if (!r.ok()) {
-                statuses[i] = static_cast<int32_t>(r.code());
-                break;
-              }
-            }
-          }
-          if (cfg.checksum && statuses[i] == 0)
-            digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
+  fan_out(items.size(), opts_.io_threads, [&](size_t i) {
+    if (statuses[i] != 0) return;
+    for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
+      const wire::Place& p = pl.places_of(pl.items[i])[c];
+      const PoolRef& pr = pools[p.pool_idx];
+      if (pr.base) {
+        std::memcpy(pr.base + p.offset, items[i].data, items[i].size);
+      } else {
+        auto r = write_shard(pr.shard(p.offset, items[i].size), items[i].data);
+        if (!r.ok()) {
+          statuses[i] = static_cast<int32_t>(r.code());
+          break;
         }
-      }));
-    for (auto& f : futs) f.get();
-  }
+      }
+    }
+    if (cfg.checksum && statuses[i] == 0)
+      digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
+  });
 
   bool all_ok = token != 0;
   for (auto st : statuses)
@@ -805,21 +749,12 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
     sess->token = 0;
   }
   if (!committed) {
-    std::vector<PutCompleteRequest> completes;
-    std::vector<ObjectKey> cancels;
-    std::vector<uint32_t> complete_idx;
-    for (size_t i = 0; i < items.size(); ++i) {
-      if (statuses[i] != 0) {
-        if (statuses[i] != static_cast<int32_t>(ErrorCode::OBJECT_EXISTS) &&
-            statuses[i] != static_cast<int32_t>(ErrorCode::NO_SPACE))
-          cancels.push_back(items[i].key);
-        continue;
-      }
-      completes.push_back(PutCompleteRequest{items[i].key, digests[i], {}});
-      complete_idx.push_back(static_cast<uint32_t>(i));
-    }
-    BB_RETURN_IF_ERROR(complete_by_keys(completes, complete_idx, &statuses));
-    cancel_puts(cancels);
+    auto cancellable = [&](size_t i) {
+      return statuses[i] != static_cast<int32_t>(ErrorCode::OBJECT_EXISTS) &&
+             statuses[i] != static_cast<int32_t>(ErrorCode::NO_SPACE);
+    };
+    BB_RETURN_IF_ERROR(
+        finish_puts(items, digests, statuses, nullptr, cancellable));
   }
   return statuses;
 }
@@ -833,11 +768,9 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once_v2(
   wire::BatchPlacements pl;
   BB_RETURN_IF_ERROR(
       wire::decode_get_workers2_response(resp.value(), keys.size(), pl));
-  std::vector<HostPoolRef> pools(pl.pools.size());
-  for (size_t i = 0; i < pools.size(); ++i) {
-    pools[i].pool_id = pl.pools[i];
-    pools[i].base = host_pool_base(pools[i].pool_id, &pools[i].access);
-  }
+  const auto pools = resolve_pool_table(
+      pl.pools,
+      [this](const PoolId& id, AccessInfo* a) { return host_pool_base(id, a); });
 
   std::vector<std::pair<int32_t, std::string>> out(keys.size());
   for (size_t i = 0; i < keys.size(); ++i) {
@@ -848,47 +781,50 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once_v2(
   }
   if (*fallback) return out;
 
-  std::atomic<size_t> next{0};
-  const int nthreads = std::max(
-      1, std::min<int>(opts_.io_threads, static_cast<int>(keys.size())));
-  std::vector<std::future<void>> futs;
-  for (int t = 0; t < nthreads; ++t)
-    futs.push_back(std::async(std::launch::async, [&] {
-      for (size_t i = next.fetch_add(1); i < keys.size();
-           i = next.fetch_add(1)) {
-        if (out[i].first != 0) continue;
-        const uint64_t size = out[i].second.size();
-        Error last{ErrorCode::NO_PLACEMENT, "no copies"};
-        bool done = false;
-        const uint64_t want = pl.items[i].checksum;
-        for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
-          const wire::Place& p = pl.places_of(pl.items[i])[c];
-          if (p.pool_idx >= pools.size()) continue;  // unknown pool: skip copy
-          HostPoolRef& pr = pools[p.pool_idx];
-          if (pr.base) {
-            std::memcpy(out[i].second.data(), pr.base + p.offset, size);
-            done = true;
-          } else {
-            auto r = read_shard(pr.shard(p.offset, size), out[i].second.data());
-            if (r.ok()) done = true;
-            else last = r.error();
-          }
-          if (done && opts_.verify_checksum_on_get && want != 0) {
-            if (gpu::checksum_cpu(out[i].second.data(), size) != want) {
-              done = false;  // corrupt copy: try the next one
-              last = Error{ErrorCode::CHECKSUM_MISMATCH, keys[i]};
-            }
-          }
-          if (done) break;
-        }
-        if (!done) {
-          out[i].first = static_cast<int32_t>(last.code);
-          out[i].second.clear();
+  fan_out(keys.size(), opts_.io_threads, [&](size_t i) {
+    if (out[i].first != 0) return;
+    const uint64_t size = out[i].second.size();
+    Error last{ErrorCode::NO_PLACEMENT, "no copies"};
+    bool done = false;
+    const uint64_t want = pl.items[i].checksum;
+    for (uint8_t c = 0; c < pl.items[i].ncopies; ++c) {
+      const wire::Place& p = pl.places_of(pl.items[i])[c];
+      if (p.pool_idx >= pools.size()) continue;  // unknown pool: skip copy
+      const PoolRef& pr = pools[p.pool_idx];
+      if (pr.base) {
+        std::memcpy(out[i].second.data(), pr.base + p.offset, size);
+        done = true;
+      } else {
+        auto r = read_shard(pr.shard(p.offset, size), out[i].second.data());
+        if (r.ok()) done = true;
+        else last = r.error();
+      }
+      if (done && opts_.verify_checksum_on_get && want != 0) {
+        if (gpu::checksum_cpu(out[i].second.data(), size) != want) {
+          done = false;  // corrupt copy: try the next one
+          last = Error{ErrorCode::CHECKSUM_MISMATCH, keys[i]};
         }
       }
-    }));
-  for (auto& f : futs) f.get();
+      if (done) break;
+    }
+    if (!done) {
+      out[i].first = static_cast<int32_t>(last.code);
+      out[i].second.clear();
+    }
+  });
   return out;
+}
+
+bool Client::bucket_copy(size_t item, const CopyPlacement& copy,
+                         EndpointBuckets& out) {
+  uint64_t off = 0;
+  for (const auto& sh : copy.shards) {
+    auto a = pool_access(sh.pool_id);
+    if (!a.ok()) return false;
+    out[a.value().endpoint].push_back({item, &sh, off});
+    off += sh.length;
+  }
+  return true;
 }
 
 Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& items,
@@ -907,33 +843,23 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
   std::vector<int32_t> statuses(items.size(), 0);
   std::vector<uint64_t> digests(items.size(), 0);
   // epilogue of both transfer strategies below: complete what transferred
-  // (striped copies carry per-shard digests), cancel what did not
+  // (striped copies carry per-shard digests), cancel what did not; an item
+  // whose placement failed is never cancelled
   auto finish = [&]() -> Result<std::vector<int32_t>> {
-    std::vector<PutCompleteRequest> completes;
-    std::vector<ObjectKey> cancels;
-    std::vector<uint32_t> complete_idx;
-    for (size_t i = 0; i < items.size(); ++i) {
-      if (start->items[i].status != 0) continue;  // placement failed
-      if (statuses[i] != 0) {
-        cancels.push_back(items[i].key);
-        continue;
-      }
-      PutCompleteRequest pc{items[i].key, digests[i], {}};
-      if (cfg.checksum)
-        pc.shard_digests =
-            host_shard_digests(start->items[i].copies, items[i].data);
-      completes.push_back(std::move(pc));
-      complete_idx.push_back(static_cast<uint32_t>(i));
-    }
-    BB_RETURN_IF_ERROR(complete_by_keys(completes, complete_idx, &statuses));
-    cancel_puts(cancels);
+    std::function<std::vector<std::vector<uint64_t>>(size_t)> shard_digests;
+    if (cfg.checksum)
+      shard_digests = [&](size_t i) {
+        return host_shard_digests(start->items[i].copies, items[i].data);
+      };
+    BB_RETURN_IF_ERROR(
+        finish_puts(items, digests, statuses, shard_digests,
+                    [&](size_t i) { return start->items[i].status == 0; }));
     return statuses;
   };
 
   if (opts_.force_tcp) {
     // one DATA_BATCH_WRITE per worker endpoint instead of one RPC per shard
-    std::map<std::string, BatchWriteEnc> per_ep;
-    std::map<std::string, std::vector<size_t>> ep_items;
+    EndpointBuckets buckets;
     bool grouped = true;
     for (size_t i = 0; i < items.size() && grouped; ++i) {
       auto& item = start->items[i];
@@ -941,33 +867,28 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
         statuses[i] = item.status;
         continue;
       }
-      for (const auto& copy : item.copies) {
-        uint64_t off = 0;
-        for (const auto& sh : copy.shards) {
-          auto a = pool_access(sh.pool_id);
-          if (!a.ok()) { grouped = false; break; }
-          WriteReq w;
-          w.pool_id = sh.pool_id;
-          w.offset = sh.offset;
-          w.src = static_cast<const uint8_t*>(items[i].data) + off;
-          w.len = sh.length;
-          per_ep[a.value().endpoint].writes.push_back(w);
-          ep_items[a.value().endpoint].push_back(i);
-          off += sh.length;
-        }
-        if (!grouped) break;
-      }
+      for (const auto& copy : item.copies)
+        if (!(grouped = bucket_copy(i, copy, buckets))) break;
     }
     if (grouped) {
-      for (auto& [ep, batch] : per_ep) {
+      for (auto& [ep, shards] : buckets) {
+        BatchWriteEnc batch;
+        for (const auto& [i, sh, off] : shards) {
+          WriteReq w;
+          w.pool_id = sh->pool_id;
+          w.offset = sh->offset;
+          w.src = static_cast<const uint8_t*>(items[i].data) + off;
+          w.len = sh->length;
+          batch.writes.push_back(w);
+        }
         auto* dc = data_client(ep);
         Result<std::string> r =
             dc ? dc->call_raw(M::DATA_BATCH_WRITE, serde::to_bytes(batch),
                               opts_.rpc_timeout_ms)
                : Result<std::string>(Error{ErrorCode::CONNECT_FAILED, ep});
         if (!r.ok())
-          for (auto i : ep_items[ep])
-            statuses[i] = static_cast<int32_t>(r.code());
+          for (const auto& es : shards)
+            statuses[es.item] = static_cast<int32_t>(r.code());
       }
       if (cfg.checksum)
         for (size_t i = 0; i < items.size(); ++i)
@@ -978,31 +899,20 @@ Result<std::vector<int32_t>> Client::batch_put_once(const std::vector<PutItem>& 
   }
 
   // transfers + digests fan out across the IO pool (each object independent)
-  {
-    std::atomic<size_t> next{0};
-    const int nthreads =
-        std::max(1, std::min<int>(opts_.io_threads, static_cast<int>(items.size())));
-    std::vector<std::future<void>> futs;
-    for (int t = 0; t < nthreads; ++t)
-      futs.push_back(std::async(std::launch::async, [&] {
-        for (size_t i = next.fetch_add(1); i < items.size();
-             i = next.fetch_add(1)) {
-          auto& item = start->items[i];
-          if (item.status != 0) {
-            statuses[i] = item.status;
-            continue;
-          }
-          auto xfer = write_copies(item.copies, items[i].data, items[i].size);
-          if (!xfer.ok()) {
-            statuses[i] = static_cast<int32_t>(xfer.code());
-            continue;
-          }
-          if (cfg.checksum)
-            digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
-        }
-      }));
-    for (auto& f : futs) f.get();
-  }
+  fan_out(items.size(), opts_.io_threads, [&](size_t i) {
+    auto& item = start->items[i];
+    if (item.status != 0) {
+      statuses[i] = item.status;
+      return;
+    }
+    auto xfer = write_copies(item.copies, items[i].data, items[i].size);
+    if (!xfer.ok()) {
+      statuses[i] = static_cast<int32_t>(xfer.code());
+      return;
+    }
+    if (cfg.checksum)
+      digests[i] = gpu::checksum_cpu(items[i].data, items[i].size);
+  });
   return finish();
 }
 
@@ -1029,9 +939,8 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once(
   std::vector<std::pair<int32_t, std::string>> out(keys.size());
 
   if (opts_.force_tcp) {
-    // one DATA_BATCH_READ per worker endpoint
-    std::map<std::string, BatchReadEnc> per_ep;
-    std::map<std::string, std::vector<std::pair<size_t, uint64_t>>> slots;
+    // one DATA_BATCH_READ per worker endpoint, of each item's first copy
+    EndpointBuckets buckets;
     bool grouped = true;
     for (size_t i = 0; i < keys.size() && grouped; ++i) {
       auto& item = meta->items[i];
@@ -1044,39 +953,38 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once(
         out[i].first = static_cast<int32_t>(ErrorCode::NO_PLACEMENT);
         continue;
       }
-      uint64_t off = 0;
-      for (const auto& sh : item.info.copies[0].shards) {
-        auto a = pool_access(sh.pool_id);
-        if (!a.ok()) { grouped = false; break; }
-        per_ep[a.value().endpoint].reads.push_back(
-            ReadReq{sh.pool_id, sh.offset, sh.length});
-        slots[a.value().endpoint].emplace_back(i, off);
-        off += sh.length;
-      }
+      grouped = bucket_copy(i, item.info.copies[0], buckets);
     }
     if (grouped) {
-      for (auto& [ep, batch] : per_ep) {
+      for (const auto& bucket : buckets) {
+        const std::string& ep = bucket.first;
+        const std::vector<EndpointShard>& shards = bucket.second;
+        auto fail = [&](ErrorCode code) {
+          for (const auto& es : shards)
+            out[es.item].first = static_cast<int32_t>(code);
+        };
+        BatchReadEnc batch;
+        for (const auto& es : shards)
+          batch.reads.push_back(
+              ReadReq{es.shard->pool_id, es.shard->offset, es.shard->length});
         auto* dc = data_client(ep);
         Result<std::string> r =
             dc ? dc->call_raw(M::DATA_BATCH_READ, serde::to_bytes(batch),
                               opts_.rpc_timeout_ms)
                : Result<std::string>(Error{ErrorCode::CONNECT_FAILED, ep});
         if (!r.ok()) {
-          for (auto& [i, off] : slots[ep])
-            out[i].first = static_cast<int32_t>(r.code());
+          fail(r.code());
           continue;
         }
         serde::Dec d(r.value().data(), r.value().size());
         uint32_t n = d.num<uint32_t>();
-        if (n != batch.reads.size()) {
-          for (auto& [i, off] : slots[ep])
-            out[i].first = static_cast<int32_t>(ErrorCode::PROTOCOL_ERROR);
+        if (n != shards.size()) {
+          fail(ErrorCode::PROTOCOL_ERROR);
           continue;
         }
-        for (uint32_t j = 0; j < n; ++j) {
+        for (const auto& [i, sh, off] : shards) {
           auto payload = d.bytes();
-          auto [i, off] = slots[ep][j];
-          if (!d.ok() || payload.size() != batch.reads[j].length) {
+          if (!d.ok() || payload.size() != sh->length) {
             out[i].first = static_cast<int32_t>(ErrorCode::PROTOCOL_ERROR);
             continue;
           }
@@ -1089,26 +997,17 @@ Result<std::vector<std::pair<int32_t, std::string>>> Client::batch_get_once(
     }
   }
 
-  std::atomic<size_t> next{0};
-  const int nthreads =
-      std::max(1, std::min<int>(opts_.io_threads, static_cast<int>(keys.size())));
-  std::vector<std::future<void>> futs;
-  for (int t = 0; t < nthreads; ++t)
-    futs.push_back(std::async(std::launch::async, [&] {
-      for (size_t i = next.fetch_add(1); i < keys.size();
-           i = next.fetch_add(1)) {
-        auto& item = meta->items[i];
-        if (item.status != 0) {
-          out[i].first = item.status;
-          continue;
-        }
-        out[i].second.resize(item.info.size);
-        auto r = read_copy(item.info.copies, out[i].second.data(), item.info.size);
-        out[i].first = static_cast<int32_t>(r.code());
-        if (!r.ok()) out[i].second.clear();
-      }
-    }));
-  for (auto& f : futs) f.get();
+  fan_out(keys.size(), opts_.io_threads, [&](size_t i) {
+    auto& item = meta->items[i];
+    if (item.status != 0) {
+      out[i].first = item.status;
+      return;
+    }
+    out[i].second.resize(item.info.size);
+    auto r = read_copy(item.info.copies, out[i].second.data(), item.info.size);
+    out[i].first = static_cast<int32_t>(r.code());
+    if (!r.ok()) out[i].second.clear();
+  });
   return out;
 }
 

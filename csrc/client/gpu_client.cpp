@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "blackbird/client/batch_util.h"
 #include "blackbird/client/batch_wire.h"
 #include "blackbird/client/pool_mapper.h"
 #include "blackbird/common/trace.h"
@@ -149,21 +150,12 @@ uint8_t* GpuClient::resolve_device_ptr(const ShardPlacement& s) {
   return base ? base + s.offset : nullptr;
 }
 
-// One pool-table entry of a v2 response, resolved once per batch.
-struct GpuClient::PoolRef {
-  PoolId pool_id;
-  uint8_t* base = nullptr;  // device-visible base or nullptr
-  AccessInfo access;        // for the staged fallback
-};
-
-std::vector<GpuClient::PoolRef> GpuClient::resolve_pools(
-    const std::vector<PoolId>& ids) {
-  std::vector<PoolRef> pools(ids.size());
-  for (size_t i = 0; i < ids.size(); ++i) {
-    pools[i].pool_id = ids[i];
-    pools[i].base = resolve_pool_base(ids[i], &pools[i].access);
-  }
-  return pools;
+// The pool table of a v2 response: `base` is the device-visible base of each
+// pool, nullptr sending its ranges through staging.
+std::vector<PoolRef> GpuClient::resolve_pools(const std::vector<PoolId>& ids) {
+  return resolve_pool_table(ids, [this](const PoolId& id, AccessInfo* a) {
+    return resolve_pool_base(id, a);
+  });
 }
 
 // Routes the (user buffer ↔ pool range) transfers of one batch: a
@@ -211,12 +203,7 @@ struct GpuClient::Router {
   Result<void> add(User user, const PoolRef& pr, uint64_t offset,
                    uint64_t nbytes, uint32_t item) {
     if (pr.base) return direct(user, pr.base + offset, nbytes);
-    ShardPlacement sp;
-    sp.pool_id = pr.pool_id;
-    sp.offset = offset;
-    sp.length = nbytes;
-    sp.access = pr.access;
-    return stage(std::move(sp), user, item);
+    return stage(pr.shard(offset, nbytes), user, item);
   }
 
   // launch the fused copy list on streams_[0]
@@ -567,27 +554,20 @@ Result<void> GpuClient::staged_read_many(
     const std::vector<std::pair<ShardPlacement, void*>>& work) {
   if (work.empty()) return {};
   if (work.size() == 1) return staged_read(work[0].first, work[0].second);
-  const int nthreads = std::min<int>(kFanThreads,
-                                     static_cast<int>(work.size()));
-  std::atomic<size_t> next{0};
-  std::vector<std::future<Result<void>>> futs;
-  for (int t = 0; t < nthreads; ++t)
-    futs.push_back(std::async(std::launch::async, [&]() -> Result<void> {
-      void* buf = acquire_staging_buf();
-      if (!buf) return Error{ErrorCode::HIP_ERROR, "staging alloc"};
-      Result<void> rc{};
-      for (size_t i = next.fetch_add(1); i < work.size();
-           i = next.fetch_add(1)) {
-        auto r = staged_read_buf(work[i].first, work[i].second, buf, kFanBuf);
-        if (!r.ok()) {
-          rc = r;
-          break;
-        }
-      }
-      release_staging_buf(buf);
-      return rc;
-    }));
-  for (auto& f : futs) BB_RETURN_IF_ERROR(f.get());
+  // one staging buffer per thread; a thread stops at its first error
+  std::vector<Result<void>> rcs(kFanThreads);
+  fan_out_threads(work.size(), kFanThreads, [&](int t, auto& next) {
+    void* buf = acquire_staging_buf();
+    if (!buf) {
+      rcs[t] = Error{ErrorCode::HIP_ERROR, "staging alloc"};
+      return;
+    }
+    for (size_t i; rcs[t].ok() && next(i);)
+      rcs[t] = staged_read_buf(work[i].first, work[i].second, buf, kFanBuf);
+    release_staging_buf(buf);
+  });
+  for (auto& r : rcs)
+    if (!r.ok()) return r.error();
   return {};
 }
 

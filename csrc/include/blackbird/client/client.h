@@ -18,6 +18,7 @@
 #include <mutex>
 #include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "blackbird/common/result.h"
@@ -156,16 +157,33 @@ class Client {
     return out;
   }
 
-  // low-level (bench/bindings): transfer one already-placed object
+ private:
+  friend class GpuClient;
+  // Moves one shard between `user` and its pool over the first rung that
+  // works: same-process pool (host memcpy, device copy, unmapped backend),
+  // SHM mapping, HIP-IPC mapping, TCP. force_tcp goes straight to TCP.
+  template <bool Write>
+  Result<void> move_shard(const ShardPlacement& s,
+                          std::conditional_t<Write, const void*, void*> user);
+  Result<void> write_shard(const ShardPlacement& s, const void* src);
+  Result<void> read_shard(const ShardPlacement& s, void* dst);
+  // write every copy (first error aborts) / read the first copy that reads
+  // completely (a copy that does not cover the object is skipped)
   Result<void> write_copies(const std::vector<CopyPlacement>& copies,
                             const void* data, uint64_t size);
   Result<void> read_copy(const std::vector<CopyPlacement>& copies, void* dst,
                          uint64_t size);
-
- private:
-  friend class GpuClient;
-  Result<void> write_shard(const ShardPlacement& s, const void* src);
-  Result<void> read_shard(const ShardPlacement& s, void* dst);
+  // One shard of a force_tcp batch and where it sits in its item's buffer,
+  // bucketed under the worker endpoint that serves it.
+  struct EndpointShard {
+    size_t item;
+    const ShardPlacement* shard;
+    uint64_t offset;
+  };
+  using EndpointBuckets = std::map<std::string, std::vector<EndpointShard>>;
+  // false: a pool of `copy` is unknown, the batch cannot be grouped
+  bool bucket_copy(size_t item, const CopyPlacement& copy,
+                   EndpointBuckets& out);
   rpc::RpcClient* data_client(const std::string& endpoint);
   // Pool access cache: batch responses omit per-shard AccessInfo (the pool
   // table is fetched once and invalidated by view_version — the reference's
@@ -189,6 +207,16 @@ class Client {
                                 std::vector<int32_t>* statuses);
   // BATCH_PUT_CANCEL (best effort; nothing is sent for an empty list)
   void cancel_puts(const std::vector<ObjectKey>& keys);
+  // Epilogue of the host batch puts that commit by key: completes the items
+  // whose status is 0 (with shard_digests_of(i) when one is given), writes
+  // per-item commit failures back into statuses, then cancels the failed
+  // items that cancellable(i) admits.
+  Result<void> finish_puts(
+      const std::vector<PutItem>& items, const std::vector<uint64_t>& digests,
+      std::vector<int32_t>& statuses,
+      const std::function<std::vector<std::vector<uint64_t>>(size_t)>&
+          shard_digests_of,
+      const std::function<bool(size_t)>& cancellable);
 
   ClientOptions opts_;
   rpc::RpcClient meta_;

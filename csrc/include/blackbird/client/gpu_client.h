@@ -28,6 +28,7 @@
 namespace blackbird {
 
 class RcclEngine;
+struct PoolRef;  // batch_util.h
 
 class GpuClient {
  public:
@@ -176,7 +177,7 @@ class GpuClient {
   uint8_t* resolve_pool_base(const PoolId& pool_id,
                              AccessInfo* access = nullptr,
                              const AccessInfo* hint = nullptr);
-  struct PoolRef;  // resolved pool-table entry of a v2 response
+  // the pool table of a v2 response, each pool resolved once
   std::vector<PoolRef> resolve_pools(const std::vector<PoolId>& ids);
   // routes a batch's transfers: fused copy list, SDMA streams or staging
   template <bool Put>
