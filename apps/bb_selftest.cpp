@@ -17,6 +17,7 @@
 #include "blackbird/coord/coord.h"
 #include "blackbird/keystone/keystone_rpc.h"
 #include "blackbird/keystone/keystone_service.h"
+#include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/rpc.h"
 
@@ -161,10 +162,352 @@ void keystone_storm() {
   CHECK(ks.get_cluster_stats().total_used == 0);
 }
 
-struct PutCompleteListMsg {
-  std::vector<PutCompleteRequest> reqs;
-  BB_FIELDS(reqs)
+// ---- keystone_transitions: the object state machine, one table per
+// transition. Deterministic and single-threaded: every route into a
+// transition must give the same answer for the same prior state. Each cell
+// prints one row (the rows are what profiles/keystone_transitions_checks.md
+// records).
+
+constexpr uint64_t kObj = 65536;
+
+std::unique_ptr<KeystoneService> table_keystone() {
+  KeystoneConfig cfg;
+  cfg.gc_interval_ms = 100000;  // no maintenance pass inside a table
+  auto ks = std::make_unique<KeystoneService>(
+      cfg, std::make_shared<coord::InProcCoord>(
+               std::make_shared<coord::CoordStore>()));
+  CHECK(ks->initialize().ok());
+  CHECK(ks->start().ok());
+  for (int i = 0; i < 4; ++i) {
+    MemoryPool p;
+    p.pool_id = "tp" + std::to_string(i);
+    p.worker_id = "tw" + std::to_string(i);
+    p.storage_class = StorageClass::RAM_CPU;
+    p.size = 1ull << 28;
+    ks->register_pool(p);
+  }
+  return ks;
+}
+
+int32_t code_of(ErrorCode c) { return static_cast<int32_t>(c); }
+
+bool same_placement(const std::vector<CopyPlacement>& a,
+                    const std::vector<CopyPlacement>& b) {
+  if (a.size() != b.size()) return false;
+  for (size_t c = 0; c < a.size(); ++c)
+    if (a[c].shards != b[c].shards) return false;  // pool, offset, length
+  return true;
+}
+
+enum Prior { ABSENT, PENDING, SAME, OTHER_SIZE, OTHER_REPL, EXPIRED, kPriors };
+enum Route { PUT_START, BATCH_OF_1, UNIFORM_8, NON_UNIFORM, kRoutes };
+const char* const kPriorName[] = {"absent",     "pending",    "same",
+                                  "other_size", "other_repl", "expired"};
+const char* const kRouteName[] = {"put_start", "batch_of_1", "uniform_8",
+                                  "non_uniform"};
+
+struct Admitted {
+  int32_t status = 0;
+  size_t copies = 0, shards = 0;
+  bool same_place = false;  // returned placement == the prior one
+  bool erased = false;      // the prior meta was dropped (sessions went stale)
+  uint64_t used = 0;        // total_used minus the batch's filler items
+  int32_t get_code = 0;     // get_workers afterwards
+  bool operator==(const Admitted& o) const {
+    return status == o.status && copies == o.copies && shards == o.shards &&
+           same_place == o.same_place && erased == o.erased &&
+           used == o.used && get_code == o.get_code;
+  }
 };
+
+// `key`/`size` through one route; fillers ride along in the batch routes
+BatchPutStartItem admit_via(KeystoneService& ks, Route route,
+                            const ObjectKey& key, uint64_t size, bool replace,
+                            uint64_t* filler_bytes) {
+  PlacementConfig pc;
+  pc.replace = replace;
+  *filler_bytes = 0;
+  BatchPutStartItem item;
+  if (route == PUT_START) {
+    auto r = ks.put_start(key, size, pc);
+    item.status = code_of(r.code());
+    if (r.ok()) item.copies = r.value().copies;
+    return item;
+  }
+  std::vector<PutStartRequest> reqs;
+  size_t at = 0;
+  if (route == BATCH_OF_1) {
+    reqs.push_back({key, size, pc});
+  } else if (route == UNIFORM_8) {
+    for (int i = 0; i < 8; ++i)
+      reqs.push_back({"filler" + std::to_string(i), kObj, pc});
+    at = 3;
+    reqs[at] = {key, size, pc};
+    *filler_bytes = 7 * kObj;
+  } else {
+    PlacementConfig other = pc;
+    other.ttl_ms = 1000000;  // a second TTL: the batch is not uniform
+    reqs.push_back({key, size, pc});
+    reqs.push_back({"filler", kObj, other});
+    *filler_bytes = kObj;
+  }
+  auto resp = ks.batch_put_start(reqs);
+  CHECK(resp.items.size() == reqs.size());
+  for (size_t i = 0; i < resp.items.size(); ++i)
+    if (i != at) CHECK(resp.items[i].status == 0);
+  return resp.items[at];
+}
+
+Admitted admission_cell(Prior prior, bool replace, Route route) {
+  auto ks = table_keystone();
+  const ObjectKey key = "k";
+  PlacementConfig pc;
+  if (prior == OTHER_REPL) pc.replication = 2;
+  if (prior == EXPIRED) pc.ttl_ms = 5;
+  std::vector<CopyPlacement> before;
+  uint64_t token = 0;
+  if (prior != ABSENT) {
+    auto r = ks->put_start(key, prior == OTHER_SIZE ? 2 * kObj : kObj, pc);
+    CHECK(r.ok());
+    before = r.value().copies;
+    if (prior != PENDING) CHECK(ks->put_complete(key, 7).ok());
+    // a session on the prior object goes stale exactly when its meta is
+    // erased; an in-place upsert keeps it current
+    token = ks->create_put_session({{key, 0, pc}});
+    CHECK(token != 0);
+    if (prior == EXPIRED)
+      std::this_thread::sleep_for(std::chrono::milliseconds(12));
+  }
+  uint64_t filler = 0;
+  auto item = admit_via(*ks, route, key, kObj, replace, &filler);
+  Admitted a;
+  a.status = item.status;
+  a.copies = item.copies.size();
+  for (const auto& c : item.copies) a.shards += c.shards.size();
+  a.same_place = item.status == 0 && same_placement(item.copies, before);
+  a.used = ks->get_cluster_stats().total_used - filler;
+  a.get_code = code_of(ks->get_workers(key).code());
+  if (token)
+    a.erased = ks->upsert_start_token(token).code() == ErrorCode::SESSION_STALE;
+  ks->stop();
+  std::printf("  admission %-10s replace=%d %-11s status=%d copies=%zu "
+              "shards=%zu same_place=%d erased=%d used=%llu get=%d\n",
+              kPriorName[prior], replace, kRouteName[route], a.status,
+              a.copies, a.shards, a.same_place, a.erased,
+              static_cast<unsigned long long>(a.used), a.get_code);
+  return a;
+}
+
+void admission_table() {
+  const int32_t exists = code_of(ErrorCode::OBJECT_EXISTS);
+  const int32_t pending = code_of(ErrorCode::OBJECT_NOT_COMMITTED);
+  //                     status copies shards same   erased used      get
+  const Admitted fresh    {0,      1, 1, false, false, kObj,     pending};
+  const Admitted replaced {0,      1, 1, false, true,  kObj,     pending};
+  const Admitted in_place {0,      1, 1, true,  false, kObj,     pending};
+  const Admitted kept     {exists, 0, 0, false, false, kObj,     0};
+  const Admitted kept_big {exists, 0, 0, false, false, 2 * kObj, 0};
+  const Admitted kept_pend{exists, 0, 0, false, false, kObj,     pending};
+  // expected[prior][replace]
+  const Admitted expected[kPriors][2] = {
+      /* absent     */ {fresh, fresh},
+      /* pending    */ {kept_pend, replaced},
+      /* same       */ {kept, in_place},
+      /* other_size */ {kept_big, replaced},
+      /* other_repl */ {kept_big, replaced},
+      /* expired    */ {replaced, in_place},
+  };
+  for (int p = 0; p < kPriors; ++p)
+    for (int replace = 0; replace < 2; ++replace)
+      for (int r = 0; r < kRoutes; ++r) {
+        auto got = admission_cell(static_cast<Prior>(p), replace,
+                                  static_cast<Route>(r));
+        Admitted want = expected[p][replace];
+        // a dropped range may be handed out again at once: equal placement
+        // proves an in-place upsert only together with erased == false
+        if (want.erased) want.same_place = got.same_place;
+        CHECK(got == want);
+      }
+  // malformed requests: refused on every route, nothing allocated
+  for (int r = 0; r < kRoutes; ++r)
+    for (int zero_size = 0; zero_size < 2; ++zero_size) {
+      auto ks = table_keystone();
+      uint64_t filler = 0;
+      auto item = admit_via(*ks, static_cast<Route>(r),
+                            zero_size ? "k" : "", zero_size ? 0 : kObj, false,
+                            &filler);
+      const uint64_t used = ks->get_cluster_stats().total_used - filler;
+      ks->stop();
+      std::printf("  admission %-10s replace=0 %-11s status=%d copies=%zu "
+                  "used=%llu\n",
+                  zero_size ? "zero_size" : "empty_key",
+                  kRouteName[r], item.status, item.copies.size(),
+                  static_cast<unsigned long long>(used));
+      CHECK(item.status == code_of(ErrorCode::INVALID_ARGUMENT));
+      CHECK(item.copies.empty());
+      CHECK(used == 0);
+    }
+}
+
+enum CommitRoute { PUT_COMPLETE, BATCH_COMPLETE, TOKEN, kCommitRoutes };
+const char* const kCommitName[] = {"put_complete", "batch_put_complete",
+                                   "commit_token"};
+
+int32_t complete_via(KeystoneService& ks, CommitRoute route,
+                     const ObjectKey& key, uint64_t checksum,
+                     const std::vector<std::vector<uint64_t>>& sd = {}) {
+  if (route == PUT_COMPLETE)
+    return code_of(ks.put_complete(key, checksum, sd).code());
+  auto st = ks.batch_put_complete({{key, checksum, sd}});
+  CHECK(st.size() == 1);
+  return st.empty() ? -1 : st[0];
+}
+
+// committed, carrying `checksum`, with `digests` on the shards of every copy
+// — as seen through all four read routes
+void check_committed(KeystoneService& ks, const ObjectKey& key,
+                     uint64_t checksum, size_t copies,
+                     const std::vector<uint64_t>& digests) {
+  CHECK(ks.object_exists(key));
+  auto listed = ks.list_objects("");
+  CHECK(listed.size() == 1 && listed[0].key == key &&
+        listed[0].ncopies == copies);
+  auto one = ks.get_workers(key);
+  auto many = ks.batch_get_workers({key});
+  CHECK(one.ok());
+  CHECK(many.items.size() == 1 && many.items[0].status == 0);
+  if (!one.ok() || many.items.size() != 1) return;
+  for (const GetWorkersResponse* info : {&one.value(), &many.items[0].info}) {
+    CHECK(info->checksum == checksum && info->size == kObj);
+    CHECK(info->copies.size() == copies);
+    for (const auto& c : info->copies) {
+      CHECK(c.shards.size() == digests.size());
+      for (size_t s = 0; s < c.shards.size() && s < digests.size(); ++s)
+        CHECK(c.shards[s].digest == digests[s]);
+    }
+  }
+}
+
+void commit_table() {
+  const ObjectKey key = "k";
+  for (uint32_t repl = 1; repl <= 2; ++repl)
+    for (int r = 0; r < kCommitRoutes; ++r) {
+      auto ks = table_keystone();
+      PlacementConfig pc;
+      pc.replication = repl;
+      CHECK(ks->put_start(key, kObj, pc).ok());
+      const auto route = static_cast<CommitRoute>(r);
+      uint64_t token = 0;
+      if (route == TOKEN) {
+        token = ks->create_put_session({{key, kObj, pc}});
+        CHECK(token != 0);
+        CHECK(ks->upsert_start_token(token).ok());
+        CHECK(ks->commit_token(token, {1, 2}).code() ==
+              ErrorCode::INVALID_ARGUMENT);  // one digest per object
+        CHECK(ks->commit_token(token, {0xC0FFEE}).ok());
+      } else {
+        CHECK(complete_via(*ks, route, key, 0xC0FFEE) == 0);
+      }
+      check_committed(*ks, key, 0xC0FFEE, repl, {0xC0FFEE});
+      if (route == TOKEN) {
+        // the session survives a plain commit; release=true ends it
+        CHECK(ks->upsert_start_token(token).ok());
+        CHECK(ks->commit_token(token, {0xBEEF}, true).ok());
+        check_committed(*ks, key, 0xBEEF, repl, {0xBEEF});
+        CHECK(ks->upsert_start_token(token).code() == ErrorCode::SESSION_STALE);
+        CHECK(ks->commit_token(token, {0xBEEF}).code() ==
+              ErrorCode::SESSION_STALE);
+        CHECK(ks->token_commits() == 2);
+      } else {
+        // a retried commit: same checksum succeeds, another one does not
+        CHECK(complete_via(*ks, route, key, 0xC0FFEE) == 0);
+        CHECK(complete_via(*ks, route, key, 0xBAD) ==
+              code_of(ErrorCode::INVALID_STATE));
+        check_committed(*ks, key, 0xC0FFEE, repl, {0xC0FFEE});
+        CHECK(complete_via(*ks, route, "missing", 1) ==
+              code_of(ErrorCode::OBJECT_NOT_FOUND));
+      }
+      ks->stop();
+      std::printf("  commit    repl=%u %-18s committed, digest on %u copies\n",
+                  repl, kCommitName[r], repl);
+    }
+  // a two-shard striped copy: per-shard digests need the right shape
+  for (int r = 0; r < TOKEN; ++r)
+    for (int wrong_shape = 0; wrong_shape < 2; ++wrong_shape) {
+      auto ks = table_keystone();
+      PlacementConfig pc;
+      pc.max_workers_per_copy = 2;
+      auto placed = ks->put_start(key, kObj, pc);
+      CHECK(placed.ok() && placed.value().copies.size() == 1 &&
+            placed.value().copies[0].shards.size() == 2);
+      CHECK(ks->create_put_session({{key, kObj, pc}}) == 0);  // single-shard only
+      std::vector<std::vector<uint64_t>> sd = {{11, 22}};
+      if (wrong_shape) sd = {{11}};
+      CHECK(complete_via(*ks, static_cast<CommitRoute>(r), key, 0xC0FFEE, sd) == 0);
+      check_committed(*ks, key, 0xC0FFEE, 1,
+                      wrong_shape ? std::vector<uint64_t>{0, 0}
+                                  : std::vector<uint64_t>{11, 22});
+      ks->stop();
+      std::printf("  commit    striped %-18s %s\n", kCommitName[r],
+                  wrong_shape ? "wrong shape: digests untouched"
+                              : "digests recorded per shard");
+    }
+}
+
+void read_table() {
+  struct Row {
+    const char* name;
+    bool visible;
+    ErrorCode get;
+  };
+  const Row rows[] = {{"absent", false, ErrorCode::OBJECT_NOT_FOUND},
+                      {"pending", false, ErrorCode::OBJECT_NOT_COMMITTED},
+                      {"committed", true, ErrorCode::OK},
+                      {"expired", false, ErrorCode::OBJECT_EXPIRED}};
+  for (int state = 0; state < 4; ++state)
+    for (int batch_get = 0; batch_get < 2; ++batch_get) {
+      auto ks = table_keystone();
+      const ObjectKey key = "k";
+      PlacementConfig pc;
+      if (state == 3) pc.ttl_ms = 5;
+      if (state >= 1) CHECK(ks->put_start(key, kObj, pc).ok());
+      if (state >= 2) CHECK(ks->put_complete(key, 7).ok());
+      if (state == 3)
+        std::this_thread::sleep_for(std::chrono::milliseconds(12));
+      auto get = [&] {
+        if (!batch_get) return code_of(ks->get_workers(key).code());
+        auto resp = ks->batch_get_workers({key});
+        CHECK(resp.items.size() == 1);
+        return resp.items.empty() ? -1 : resp.items[0].status;
+      };
+      const Row& row = rows[state];
+      const bool exists = ks->object_exists(key);
+      const size_t listed = ks->list_objects("").size();
+      CHECK(exists == row.visible);
+      CHECK(ks->batch_object_exists({key}) == std::vector<uint8_t>{exists});
+      CHECK(listed == (row.visible ? 1u : 0u));
+      const int32_t first = get();
+      CHECK(first == code_of(row.get));
+      if (state == 3) {
+        // either get route removes the expired object on the way out
+        CHECK(ks->get_cluster_stats().total_used == 0);
+        CHECK(get() == code_of(ErrorCode::OBJECT_NOT_FOUND));
+      } else {
+        CHECK(get() == first);
+        CHECK(ks->get_cluster_stats().total_used == (state ? kObj : 0));
+      }
+      ks->stop();
+      std::printf("  read      %-9s %-17s exists=%d listed=%zu get=%d\n",
+                  row.name, batch_get ? "batch_get_workers" : "get_workers",
+                  exists, listed, first);
+    }
+}
+
+void keystone_transitions() {
+  admission_table();
+  commit_table();
+  read_table();
+}
 
 // Mirrors the flagship bench's control-plane pattern over the REAL wire:
 // v2 batch put_start with replace=true cycling the same key space, batch
@@ -406,6 +749,7 @@ void fan_out_storm() {
 }  // namespace
 
 int main() {
+  std::setvbuf(stdout, nullptr, _IOLBF, 0);  // table rows stay whole in a log
   std::printf("pool_allocator_storm...\n");
   pool_allocator_storm();
   std::printf("range_allocator_storm...\n");
@@ -414,6 +758,8 @@ int main() {
   coord_storm();
   std::printf("keystone_storm...\n");
   keystone_storm();
+  std::printf("keystone_transitions...\n");
+  keystone_transitions();
   std::printf("v2_replace_storm...\n");
   v2_replace_storm();
   std::printf("coord_repl_storm...\n");

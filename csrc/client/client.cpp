@@ -18,6 +18,7 @@
 #include "blackbird/coord/coord.h"
 #include "blackbird/common/log.h"
 #include "blackbird/gpu/gpu_kernels.h"
+#include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/worker/storage_backend.h"
 
@@ -26,34 +27,8 @@ namespace blackbird {
 namespace M = rpc::methods;
 
 namespace {
-struct KeyMsg {
-  std::string key;
-  BB_FIELDS(key)
-};
-struct KeysMsg {
-  std::vector<std::string> keys;
-  BB_FIELDS(keys)
-};
-struct BoolMsg {
-  uint8_t v = 0;
-  BB_FIELDS(v)
-};
-struct U64Msg {
-  uint64_t v = 0;
-  BB_FIELDS(v)
-};
-struct PoolsMsg {
-  std::vector<MemoryPool> pools;
-  BB_FIELDS(pools)
-};
-struct WorkersInfoMsg {
-  std::vector<WorkerInfo> workers;
-  BB_FIELDS(workers)
-};
-struct StatusListMsg {
-  std::vector<int32_t> statuses;
-  BB_FIELDS(statuses)
-};
+// encode-only twin of the WriteReq in worker_service.cpp: the payload is
+// written straight from the caller's buffer
 struct WriteReq {
   std::string pool_id;
   uint64_t offset = 0;
@@ -65,12 +40,6 @@ struct WriteReq {
     e.bytes(src, len);
   }
   void dec(serde::Dec&) {}
-};
-struct ReadReq {
-  std::string pool_id;
-  uint64_t offset = 0;
-  uint64_t length = 0;
-  BB_FIELDS(pool_id, offset, length)
 };
 struct BatchWriteEnc {  // encodes to the worker's BatchWriteReq wire format
   std::vector<WriteReq> writes;

@@ -140,15 +140,14 @@ class KeystoneService {
   }
 
  private:
+  using ObjectMap = std::unordered_map<ObjectKey, ObjectMeta>;
+  using DirtySet = std::map<ObjectKey, bool>;  // key → removed?
+
   void gc_loop();
   void keepalive_loop();
-  void persist_loop();
-  // drain the dirty set synchronously in one coord round trip (durability
-  // of commit/remove acks); call without objects_mu_ held
-  void flush_dirty_now();
-  void mark_dirty_locked(const ObjectKey& key, bool removed);
   void setup_watchers();
   void load_existing_state();
+  void upsert_worker(WorkerInfo w);
   void handle_worker_event(const coord::WatchEvent& ev);
   void handle_pool_event(const coord::WatchEvent& ev);
   void handle_heartbeat_event(const coord::WatchEvent& ev);
@@ -157,15 +156,56 @@ class KeystoneService {
   std::string prefix() const {
     return "/blackbird/clusters/" + config_.cluster_id;
   }
-  // callers hold objects_mu_ exclusively
+
+  // ---- object transitions; the *_locked ones need objects_mu_ held
+  // exclusively ----
+  // What an incoming put of `size` bytes under `cfg` does to the object at
+  // `it` (objects_.end(): none yet).
+  enum class Admission {
+    EXISTS,    // refused: a live object and no cfg.replace
+    IN_PLACE,  // same-shape upsert: flipped to PENDING, its placement stands
+    REPLACE,   // the caller erases the object and places the key afresh
+    FRESH,     // nothing there
+  };
+  Admission admit_locked(ObjectMap::iterator it, uint64_t size,
+                         const PlacementConfig& cfg, uint64_t now);
+  ObjectMeta pending_meta(const ObjectKey& key, uint64_t size,
+                          const PlacementConfig& cfg, uint64_t now,
+                          const std::vector<CopyPlacement>& copies) const;
+  // drops the meta only; the ranges and the view are the caller's
+  void erase_locked(ObjectMap::iterator it);
+  // erase + range free + view bump
   Result<void> remove_object_locked(const ObjectKey& key);
+  // the body of both get routes, under the SHARED lock: status, and on
+  // success the touch and the answer
+  ErrorCode read_locked(const ObjectKey& key, uint64_t now,
+                        GetWorkersResponse& info);
+  void remove_if_expired_locked(const ObjectKey& key, uint64_t now);
+
+  // ---- maintenance (keystone_maintenance.cpp) ----
+  // copy of a COMMITTED object's meta, taken under the exclusive lock
+  Result<ObjectMeta> snapshot_committed(const ObjectKey& key);
+  // One DATA_PULL per destination shard: each pulls its slice of the ordered
+  // source shards. Stops at the first error.
+  Result<void> pull_into(const std::vector<ShardPlacement>& dst_shards,
+                         const std::vector<ShardPlacement>& src_shards);
+  void persist_loop();
+  void mark_dirty_locked(const ObjectKey& key, bool removed);
+  DirtySet drain_dirty();
+  // the coordination writes for `batch`; takes objects_mu_ exclusively
+  void encode_dirty(const DirtySet& batch, std::vector<coord::KV>& puts,
+                    std::vector<std::string>& dels);
+  // drain the dirty set in one fenced coord round trip, re-queueing it on
+  // failure (durability of commit/remove acks, and the persist loop's
+  // step); call without objects_mu_ held
+  void flush_dirty_now();
 
   KeystoneConfig config_;
   std::shared_ptr<coord::CoordService> coord_;
   RangeAllocator allocator_;
 
   std::shared_mutex objects_mu_;
-  std::unordered_map<ObjectKey, ObjectMeta> objects_;
+  ObjectMap objects_;
 
   // ---- put sessions ----
   // metas are raw pointers into objects_ (unordered_map mapped values are
@@ -180,6 +220,9 @@ class KeystoneService {
   };
   uint64_t placement_epoch_ = 0;  // guarded by objects_mu_ (unique)
   void bump_placement_epoch_locked() { ++placement_epoch_; }
+  std::shared_ptr<PutSession> find_session(uint64_t token);  // or null
+  // epoch and sizes still match; objects_mu_ held (shared suffices)
+  Result<void> session_current_locked(const PutSession& s) const;
   std::mutex sessions_mu_;
   std::unordered_map<uint64_t, std::shared_ptr<PutSession>> put_sessions_;
   std::atomic<uint64_t> next_session_token_{1};
@@ -201,7 +244,7 @@ class KeystoneService {
   std::thread keepalive_thread_;
   std::thread persist_thread_;
   std::mutex dirty_mu_;
-  std::map<ObjectKey, bool> dirty_;  // key → removed?
+  DirtySet dirty_;
   std::condition_variable cv_;
   std::mutex cv_mu_;
   // Small pool of connections per worker endpoint: the RPC server is

@@ -2,47 +2,17 @@
 
 #include "blackbird/client/batch_wire.h"
 #include "blackbird/common/log.h"
+#include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/net.h"
+#include "keystone_internal.h"
 
 namespace blackbird {
 
 namespace {
-struct KeyMsg {
-  std::string key;
-  BB_FIELDS(key)
-};
-struct KeysMsg {
-  std::vector<std::string> keys;
-  BB_FIELDS(keys)
-};
-struct BoolMsg {
-  uint8_t v = 0;
-  BB_FIELDS(v)
-};
-struct U64Msg {
-  uint64_t v = 0;
-  BB_FIELDS(v)
-};
-struct StatusListMsg {
-  std::vector<int32_t> statuses;
-  BB_FIELDS(statuses)
-};
-struct ExistsListMsg {
+struct ExistsListMsg {  // BATCH_OBJECT_EXISTS has no caller in this tree yet
   std::vector<uint8_t> exists;
   BB_FIELDS(exists)
-};
-struct WorkersInfoMsg {
-  std::vector<WorkerInfo> workers;
-  BB_FIELDS(workers)
-};
-struct PoolsMsg {
-  std::vector<MemoryPool> pools;
-  BB_FIELDS(pools)
-};
-struct PutCompleteListMsg {
-  std::vector<PutCompleteRequest> reqs;
-  BB_FIELDS(reqs)
 };
 
 template <typename Req>
@@ -64,90 +34,90 @@ KeystoneServer::~KeystoneServer() { stop(); }
 void KeystoneServer::register_handlers() {
   namespace M = rpc::methods;
   using Ctx = rpc::RpcServer::ConnCtx;
+  using Reply = Result<std::string>;
   auto& ks = *service_;
 
-  rpc_.register_handler(M::PING, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  // Served by any keystone.
+  auto on = [this](uint16_t method, rpc::RpcServer::Handler h) {
+    rpc_.register_handler(method, std::move(h));
+  };
+  // Served by the leader alone. A standby answers with a CALL-level error
+  // (for batches too, not per-item statuses), so the client's failover
+  // machinery rediscovers the leader and retries.
+  auto leader_only = [this, &ks](uint16_t method, auto handler) {
+    rpc_.register_handler(
+        method, [&ks, handler](const std::string& b, const Ctx& c) -> Reply {
+          if (!ks.is_leader()) return not_leader();
+          return handler(b, c);
+        });
+  };
+
+  on(M::PING, [&ks](const std::string&, const Ctx&) -> Reply {
     PingResponse p;
     p.view_version = ks.get_view_version();
     p.server_time_ms = wall_ms();
     p.is_leader = ks.is_leader();
     return serde::to_bytes(p);
   });
-  rpc_.register_handler(M::OBJECT_EXISTS, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::OBJECT_EXISTS, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(BoolMsg{static_cast<uint8_t>(ks.object_exists(r->key))});
   });
-  rpc_.register_handler(M::GET_WORKERS, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::GET_WORKERS, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);
     if (!r.ok()) return r.error();
     auto resp = ks.get_workers(r->key);
     if (!resp.ok()) return resp.error();
     return serde::to_bytes(resp.value());
   });
-  rpc_.register_handler(M::PUT_START, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::PUT_START, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<PutStartRequest>(b);
     if (!r.ok()) return r.error();
     auto resp = ks.put_start(r->key, r->size, r->config);
     if (!resp.ok()) return resp.error();
     return serde::to_bytes(resp.value());
   });
-  rpc_.register_handler(M::PUT_COMPLETE, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::PUT_COMPLETE, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<PutCompleteRequest>(b);
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(ks.put_complete(r->key, r->checksum, r->shard_digests));
     return std::string{};
   });
-  rpc_.register_handler(M::PUT_CANCEL, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::PUT_CANCEL, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(ks.put_cancel(r->key));
     return std::string{};
   });
-  rpc_.register_handler(M::REMOVE_OBJECT, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::REMOVE_OBJECT, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(ks.remove_object(r->key));
     return std::string{};
   });
-  rpc_.register_handler(M::REMOVE_ALL_OBJECTS, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::REMOVE_ALL_OBJECTS, [&ks](const std::string&, const Ctx&) -> Reply {
     return serde::to_bytes(U64Msg{ks.remove_all_objects()});
   });
-  rpc_.register_handler(M::GET_WORKERS_INFO, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  on(M::GET_WORKERS_INFO, [&ks](const std::string&, const Ctx&) -> Reply {
     return serde::to_bytes(WorkersInfoMsg{ks.get_workers_info()});
   });
-  rpc_.register_handler(M::GET_MEMORY_POOLS, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  on(M::GET_MEMORY_POOLS, [&ks](const std::string&, const Ctx&) -> Reply {
     return serde::to_bytes(PoolsMsg{ks.get_memory_pools()});
   });
-  rpc_.register_handler(M::REMOVE_WORKER, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
+  on(M::REMOVE_WORKER, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(ks.remove_worker(r->key));
     return std::string{};
   });
-  rpc_.register_handler(M::GET_CLUSTER_STATS, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  on(M::GET_CLUSTER_STATS, [&ks](const std::string&, const Ctx&) -> Reply {
     return serde::to_bytes(ks.get_cluster_stats());
   });
-  rpc_.register_handler(M::GET_VIEW_VERSION, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  on(M::GET_VIEW_VERSION, [&ks](const std::string&, const Ctx&) -> Reply {
     return serde::to_bytes(U64Msg{ks.get_view_version()});
   });
-  rpc_.register_handler(M::LIST_OBJECTS, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::LIST_OBJECTS, [&ks](const std::string& b, const Ctx&) -> Reply {
     serde::Dec d(b.data(), b.size());
     std::string prefix = d.str();
     uint32_t limit = d.num<uint32_t>();
@@ -156,56 +126,44 @@ void KeystoneServer::register_handlers() {
     serde::put(e, ks.list_objects(prefix, limit ? limit : 1000));
     return std::move(e.buf);
   });
-  rpc_.register_handler(M::ADMIN_SCRUB, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
+  on(M::ADMIN_SCRUB, [&ks](const std::string& b, const Ctx&) -> Reply {
     serde::Dec d(b.data(), b.size());
     uint32_t max_objects = d.num<uint32_t>();
     return serde::to_bytes(U64Msg{ks.run_scrub_once(d.ok() ? max_objects : 0)});
   });
-  rpc_.register_handler(M::ADMIN_REPAIR, [&ks](const std::string&, const Ctx&) -> Result<std::string> {
+  on(M::ADMIN_REPAIR, [&ks](const std::string&, const Ctx&) -> Reply {
     ks.run_repair_once();
     return std::string{};
   });
-  rpc_.register_handler(M::ADMIN_COMPACT, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
+  on(M::ADMIN_COMPACT, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeyMsg>(b);  // key = pool id
     if (!r.ok()) return r.error();
     auto moved = ks.compact_pool(r->key);
     if (!moved.ok()) return moved.error();
     return serde::to_bytes(U64Msg{moved.value()});
   });
-  rpc_.register_handler(M::BATCH_PUT_START, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    // standby answers with a CALL-level error (not per-item statuses) so the
-    // client's failover machinery rediscovers the leader and retries
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_PUT_START, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<BatchPutStartRequest>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(ks.batch_put_start(r->requests));
   });
-  rpc_.register_handler(M::BATCH_PUT_COMPLETE, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_PUT_COMPLETE, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<PutCompleteListMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(StatusListMsg{ks.batch_put_complete(r->reqs)});
   });
-  rpc_.register_handler(M::BATCH_PUT_CANCEL, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_PUT_CANCEL, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(StatusListMsg{ks.batch_put_cancel(r->keys)});
   });
-  rpc_.register_handler(M::BATCH_GET_WORKERS, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_GET_WORKERS, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(ks.batch_get_workers(r->keys));
   });
   // ---- compact v2 batch protocol: pool-table + fixed-width placements ----
-  rpc_.register_handler(M::BATCH_PUT_START2, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_PUT_START2, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto rq = wire::decode_put_start2_request(b);
     if (!rq.ok()) return rq.error();
     rq->cfg.max_workers_per_copy = 1;  // v2 contract: single-shard copies
@@ -228,9 +186,7 @@ void KeystoneServer::register_handlers() {
       wire::append_item(out, table, it.status, it.copies);
     return wire::encode_put_start2_response(out);
   });
-  rpc_.register_handler(M::BATCH_GET_WORKERS2, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_GET_WORKERS2, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto keys = wire::decode_get_workers2_request(b);
     if (!keys.ok()) return keys.error();
     auto resp = ks.batch_get_workers(keys.value());
@@ -248,28 +204,25 @@ void KeystoneServer::register_handlers() {
     }
     return wire::encode_get_workers2_response(out);
   });
-  rpc_.register_handler(M::BATCH_UPSERT_START, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
+  // the session calls refuse a standby themselves
+  on(M::BATCH_UPSERT_START, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto token = wire::decode_upsert_start(b);
     if (!token.ok()) return token.error();
     BB_RETURN_IF_ERROR(ks.upsert_start_token(token.value()));
     return std::string{};
   });
-  rpc_.register_handler(M::BATCH_COMMIT_TOKEN, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
+  on(M::BATCH_COMMIT_TOKEN, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto c = wire::decode_commit_token(b);
     if (!c.ok()) return c.error();
     BB_RETURN_IF_ERROR(ks.commit_token(c->token, c->digests, c->flags & 1));
     return std::string{};
   });
-  rpc_.register_handler(M::BATCH_REMOVE, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_REMOVE, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(StatusListMsg{ks.batch_remove(r->keys)});
   });
-  rpc_.register_handler(M::BATCH_OBJECT_EXISTS, [&ks](const std::string& b, const Ctx&) -> Result<std::string> {
-    if (!ks.is_leader())
-      return Error{ErrorCode::NOT_LEADER, "standby keystone; retry on leader"};
+  leader_only(M::BATCH_OBJECT_EXISTS, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(ExistsListMsg{ks.batch_object_exists(r->keys)});
@@ -282,19 +235,13 @@ Result<void> KeystoneServer::start() {
     BB_RETURN_IF_ERROR(rpc_.start(addr, 0));
     service_->set_advertised_endpoint(addr);
     BB_LOG(INFO) << "keystone RPC listening on " << addr;
-    if (!service_->config().metrics_address.empty()) {
-      metrics_ = std::make_unique<MetricsHttpServer>(*service_);
-      auto mr = metrics_->start(service_->config().metrics_address);
-      if (!mr.ok())
-        BB_LOG(WARN) << "metrics server failed to start: " << mr.message();
-    }
-    return {};
+  } else {
+    auto hp = net::split_endpoint(addr);
+    if (!hp.ok()) return hp.error();
+    BB_RETURN_IF_ERROR(rpc_.start(hp.value().first, hp.value().second));
+    service_->set_advertised_endpoint(rpc_.endpoint());
+    BB_LOG(INFO) << "keystone RPC listening on " << rpc_.endpoint();
   }
-  auto hp = net::split_endpoint(addr);
-  if (!hp.ok()) return hp.error();
-  BB_RETURN_IF_ERROR(rpc_.start(hp.value().first, hp.value().second));
-  service_->set_advertised_endpoint(rpc_.endpoint());
-  BB_LOG(INFO) << "keystone RPC listening on " << rpc_.endpoint();
   if (!service_->config().metrics_address.empty()) {
     metrics_ = std::make_unique<MetricsHttpServer>(*service_);
     auto mr = metrics_->start(service_->config().metrics_address);

@@ -9,6 +9,7 @@
 #include "blackbird/common/trace.h"
 #include "blackbird/common/log.h"
 #include "blackbird/gpu/gpu_kernels.h"
+#include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/rpc.h"
 
@@ -24,13 +25,6 @@ Error hip_err(hipError_t e, const char* what) {
     hipError_t _e = (expr);                           \
     if (_e != hipSuccess) return hip_err(_e, #expr);  \
   } while (0)
-
-struct ReadReq {
-  std::string pool_id;
-  uint64_t offset = 0;
-  uint64_t length = 0;
-  BB_FIELDS(pool_id, offset, length)
-};
 }  // namespace
 
 TransferEngine::TransferEngine() : mapper_(std::make_shared<PoolMapper>()) {}

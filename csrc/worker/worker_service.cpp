@@ -1,12 +1,14 @@
 #include "blackbird/worker/worker_service.h"
 
 #include "blackbird/common/log.h"
+#include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/net.h"
 
 namespace blackbird {
 
 namespace {
+// the decoding twin of client.cpp's encode-only WriteReq
 struct WriteReq {
   std::string pool_id;
   uint64_t offset = 0;
@@ -22,36 +24,13 @@ struct WriteReq {
     data = d.bytes();
   }
 };
-struct ReadReq {
-  std::string pool_id;
-  uint64_t offset = 0;
-  uint64_t length = 0;
-  BB_FIELDS(pool_id, offset, length)
-};
-struct ChecksumReq {
-  std::string pool_id;
-  uint64_t offset = 0;
-  uint64_t length = 0;
-  BB_FIELDS(pool_id, offset, length)
-};
-struct U64Msg {
-  uint64_t v = 0;
-  BB_FIELDS(v)
-};
-struct BatchWriteReq {
+struct BatchWriteReq {  // client.cpp encodes it as BatchWriteEnc
   std::vector<WriteReq> writes;
   BB_FIELDS(writes)
 };
-struct BatchReadReq {
+struct BatchReadReq {  // client.cpp encodes it as BatchReadEnc
   std::vector<ReadReq> reads;
   BB_FIELDS(reads)
-};
-struct PullReq {
-  std::string dst_pool;
-  uint64_t dst_offset = 0;
-  uint64_t total_len = 0;
-  std::vector<ShardPlacement> srcs;
-  BB_FIELDS(dst_pool, dst_offset, total_len, srcs)
 };
 
 template <typename Req>

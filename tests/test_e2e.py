@@ -251,6 +251,47 @@ class TestRepair:
         finally:
             cl.stop()
 
+    def test_repair_from_striped_survivor(self):
+        """The surviving copy is striped over two workers: the new replica
+        pulls its bytes from both source shards."""
+        cl = Cluster(n_workers=4, pool_bytes=32 * MB)
+        try:
+            c = cl.client()
+            cfg = bb.PlacementConfig()
+            cfg.replication = 2
+            cfg.max_workers_per_copy = 2
+            data = os.urandom(512 * 1024)
+            c.put("striped-fixme", data, cfg)
+            ks = cl.keystone.service()
+            info = ks.get_workers("striped-fixme")
+            assert [len(cp.shards) for cp in info.copies] == [2, 2]
+            repairs_before = ks.counters()["repairs"]
+            victim_id = info.copies[0].shards[0].worker_id
+            victim = next(w for w in cl.workers
+                          if any(p.worker_id == victim_id
+                                 for p in w.pool_descriptors()))
+            victim.stop()
+
+            def holders():
+                return {s.worker_id
+                        for cp in ks.get_workers("striped-fixme").copies
+                        for s in cp.shards}
+            deadline = time.time() + 5
+            while time.time() < deadline and victim_id in holders():
+                time.sleep(0.05)
+            assert victim_id not in holders()
+            # the fixture's gc loop repairs as well; whichever pass gets
+            # there first, the object is repaired exactly once
+            ks.run_repair_once()
+            info = ks.get_workers("striped-fixme")
+            assert len(info.copies) == 2
+            assert victim_id not in holders()
+            assert c.get("striped-fixme") == data
+            assert ks.counters()["repairs"] == repairs_before + 1
+            c.close()
+        finally:
+            cl.stop()
+
     def test_repair_waits_for_capacity(self):
         cl = Cluster(n_workers=2, pool_bytes=8 * MB)
         try:

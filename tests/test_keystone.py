@@ -575,6 +575,81 @@ class TestDurableAcks:
             cs.stop()
 
 
+    def test_maintenance_mutations_reach_coordination(self):
+        """A migration is acknowledged to nobody, so nothing flushes it
+        synchronously: the background persist loop must carry the new
+        placement into coordination, and a restarted keystone must serve
+        it."""
+        store = bb.CoordStore()
+        cs = bb.CoordServer(store)
+        cs.start("127.0.0.1", 0)
+        ep = "127.0.0.1:%d" % cs.port
+        cfg = bb.KeystoneConfig()
+        cfg.listen_address = "127.0.0.1:0"
+        cfg.coord_endpoint = ep
+        cfg.persist_objects = True
+        cfg.gc_interval_ms = 100000
+        srv = bb.create_and_start_keystone(cfg)
+        wc = bb.WorkerConfig()
+        wc.worker_id = "mw0"
+        wc.coord_endpoint = ep
+        wc.data_listen_address = "127.0.0.1:0"
+        pools = []
+        for pool_id, cls in (("mig-ram", bb.StorageClass.RAM_CPU),
+                             ("mig-cxl", bb.StorageClass.CXL_MEM)):
+            p = bb.PoolConfig()
+            p.pool_id = pool_id
+            p.storage_class = cls
+            p.size_bytes = 16 << 20
+            pools.append(p)
+        wc.pools = pools
+        w = bb.WorkerService(wc)
+        w.initialize()
+        w.start()
+        deadline = time.time() + 5
+        while (time.time() < deadline
+               and len(srv.service().get_memory_pools()) < 2):
+            time.sleep(0.02)
+        try:
+            o = bb.ClientOptions()
+            o.keystone_endpoint = srv.endpoint
+            c = bb.Client(o)
+            c.connect()
+            pc = bb.PlacementConfig()
+            pc.required_class = bb.StorageClass.RAM_CPU
+            data = b"m" * 65536
+            c.put("moved", data, pc)
+            key = "/blackbird/clusters/default/objects/moved"
+            blob = dict(store.get_prefix(key))[key]
+            assert b"mig-ram" in blob and b"mig-cxl" not in blob
+            srv.service().migrate_object("moved", bb.StorageClass.CXL_MEM)
+            deadline = time.time() + 2
+            while time.time() < deadline:
+                blob = dict(store.get_prefix(key))[key]
+                if b"mig-cxl" in blob:
+                    break
+                time.sleep(0.02)
+            # the stored meta names the pools of its shards
+            assert b"mig-cxl" in blob and b"mig-ram" not in blob
+            c.close()
+            srv.stop()
+            srv.service().stop()
+            srv = bb.create_and_start_keystone(cfg)
+            shard = srv.service().get_workers("moved").copies[0].shards[0]
+            assert shard.pool_id == "mig-cxl"
+            assert shard.storage_class == bb.StorageClass.CXL_MEM
+            o.keystone_endpoint = srv.endpoint
+            c = bb.Client(o)
+            c.connect()
+            assert c.get("moved") == data
+            c.close()
+        finally:
+            w.stop()
+            srv.stop()
+            srv.service().stop()
+            cs.stop()
+
+
 class TestFailoverMidBatch:
     def test_batches_survive_leader_failover_with_zero_errors(self):
         """a keystone leader failover in the MIDDLE of a batch
