@@ -388,7 +388,8 @@ PYBIND11_MODULE(_core, m) {
   // Test-only: the v2 batch wire codec (batch_wire.h), one message per call.
   // Values travel as dicts so the tests can hand-build them; `msg` is one of
   // put_start2_req, put_start2_resp, get_workers2_req, get_workers2_resp,
-  // upsert_start, commit_token. Decoding a malformed body raises
+  // upsert_start, commit_token, session_open, session_open_resp,
+  // commit_token_shards. Decoding a malformed body raises
   // PROTOCOL_ERROR.
   m.def("batch_wire_encode_for_test", [](const std::string& msg, py::dict v) {
     struct Item {
@@ -442,6 +443,21 @@ PYBIND11_MODULE(_core, m) {
       out = wire::encode_commit_token(v["token"].cast<uint64_t>(),
                                       v["release"].cast<bool>(), dg.data(),
                                       dg.size());
+    } else if (msg == "session_open") {
+      std::vector<Item> items;
+      for (auto h : v["items"]) {
+        auto t = h.cast<std::pair<std::string, uint64_t>>();
+        items.push_back({t.first, t.second});
+      }
+      out = wire::encode_session_open(items, v["allow_striped"].cast<bool>());
+    } else if (msg == "session_open_resp") {
+      out = wire::encode_session_open_response(v["token"].cast<uint64_t>());
+    } else if (msg == "commit_token_shards") {
+      auto od = v["obj_digests"].cast<std::vector<uint64_t>>();
+      auto sd = v["shard_digests"].cast<std::vector<uint64_t>>();
+      out = wire::encode_commit_token_shards(
+          v["token"].cast<uint64_t>(), v["release"].cast<bool>(), od.data(),
+          od.size(), sd.data(), sd.size());
     } else {
       throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
     }
@@ -498,6 +514,21 @@ PYBIND11_MODULE(_core, m) {
             v["token"] = c.token;
             v["release"] = (c.flags & 1) != 0;
             v["digests"] = c.digests;
+          } else if (msg == "session_open") {
+            auto r = unwrap(wire::decode_session_open(body));
+            py::list items;
+            for (size_t i = 0; i < r.keys.size(); ++i)
+              items.append(py::make_tuple(r.keys[i], r.sizes[i]));
+            v["items"] = items;
+            v["allow_striped"] = (r.flags & 1) != 0;
+          } else if (msg == "session_open_resp") {
+            v["token"] = unwrap(wire::decode_session_open_response(body));
+          } else if (msg == "commit_token_shards") {
+            auto c = unwrap(wire::decode_commit_token_shards(body));
+            v["token"] = c.token;
+            v["release"] = (c.flags & 1) != 0;
+            v["obj_digests"] = c.obj_digests;
+            v["shard_digests"] = c.shard_digests;
           } else {
             throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
           }
@@ -635,6 +666,36 @@ PYBIND11_MODULE(_core, m) {
            for (auto& step : out) unwrap_void(plan.run(step.data()));
            return out;
          }, py::arg("descs"), py::arg("steps"), py::arg("device") = 0);
+  // one FusedStripePlan, replayed `steps` times: one (segment digests, object
+  // digests) pair per step, poisoned before each run as in fused_stripe.
+  // before_step(k), when given, runs before replay k (a test rewrites the
+  // source there).
+  gm.def("fused_stripe_plan",
+         [to_stripe_segs](const SegTuples& segs,
+                          const std::vector<uint64_t>& obj_sizes, int steps,
+                          int device, py::object before_step) {
+           auto ss = to_stripe_segs(segs);
+           std::vector<std::pair<std::vector<uint64_t>, std::vector<uint64_t>>>
+               out;
+           gpu::FusedStripePlan plan;
+           {
+             py::gil_scoped_release rel;
+             unwrap_void(plan.build(ss.data(), static_cast<uint32_t>(ss.size()),
+                                    obj_sizes.data(),
+                                    static_cast<uint32_t>(obj_sizes.size()),
+                                    device));
+           }
+           for (int k = 0; k < steps; ++k) {
+             if (!before_step.is_none()) before_step(k);
+             out.emplace_back(std::vector<uint64_t>(ss.size(), ~0ull),
+                              std::vector<uint64_t>(obj_sizes.size(), ~0ull));
+             py::gil_scoped_release rel;
+             unwrap_void(plan.run(out.back().first.data(),
+                                  out.back().second.data()));
+           }
+           return out;
+         }, py::arg("segs"), py::arg("obj_sizes"), py::arg("steps"),
+         py::arg("device") = 0, py::arg("before_step") = py::none());
   gm.def("batched_copy",
          [](const std::vector<std::tuple<uint64_t, uint64_t, uint64_t>>& descs) {
            std::vector<gpu::CopyDesc> ds;

@@ -204,12 +204,22 @@ void bind_store(py::module_& m) {
       // sessionful upsert protocol (CPU-testable surface)
       .def("create_put_session", [](KeystoneService& k,
                                     const std::vector<std::string>& keys,
-                                    uint64_t size, const PlacementConfig& cfg) {
+                                    uint64_t size, const PlacementConfig& cfg,
+                                    bool allow_striped) {
         std::vector<PutStartRequest> reqs;
         reqs.reserve(keys.size());
         for (auto& key : keys) reqs.push_back({key, size, cfg});
-        return k.create_put_session(reqs);
-      })
+        return k.create_put_session(reqs, allow_striped);
+      }, py::arg("keys"), py::arg("size"), py::arg("config"),
+         py::arg("allow_striped") = false)
+      .def("commit_token_shards", [](KeystoneService& k, uint64_t token,
+                                     const std::vector<uint64_t>& obj_digests,
+                                     const std::vector<uint64_t>& shard_digests,
+                                     bool release) {
+        unwrap_void(k.commit_token_shards(token, obj_digests, shard_digests,
+                                          release));
+      }, py::arg("token"), py::arg("obj_digests"), py::arg("shard_digests"),
+         py::arg("release") = false)
       .def("upsert_start_token", [](KeystoneService& k, uint64_t token) {
         unwrap_void(k.upsert_start_token(token));
       })
@@ -381,6 +391,25 @@ void bind_store(py::module_& m) {
              return unwrap(c.batch_put(its, cfg, &sess));
            },
            py::arg("items"), py::arg("config"), py::arg("session"))
+      // BATCH_SESSION_OPEN / BATCH_COMMIT_TOKEN_SHARDS as the GPU client
+      // sends them (objects: (key, size) pairs); token 0 = refused
+      .def("open_session",
+           [](Client& c,
+              const std::vector<std::pair<std::string, uint64_t>>& objects,
+              bool allow_striped) {
+             return unwrap(c.open_session(objects, allow_striped));
+           }, py::arg("objects"), py::arg("allow_striped") = false,
+           py::call_guard<py::gil_scoped_release>())
+      .def("commit_by_token_shards",
+           [](Client& c, uint64_t token,
+              const std::vector<uint64_t>& obj_digests,
+              const std::vector<uint64_t>& shard_digests, bool release) {
+             unwrap_void(c.commit_by_token_shards(
+                 token, release, obj_digests.data(), obj_digests.size(),
+                 shard_digests.data(), shard_digests.size()));
+           }, py::arg("token"), py::arg("obj_digests"),
+           py::arg("shard_digests"), py::arg("release") = false,
+           py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("host_session_steps",
                              &Client::host_session_steps)
       .def("batch_get", [](Client& c, const std::vector<std::string>& keys) {
@@ -504,6 +533,13 @@ void bind_store(py::module_& m) {
                if (v != 0) return false;
              return true;
            }, py::arg("batch"), py::arg("verify") = false)
+      // the per-item statuses of a prepared get (batch_get_prepared folds
+      // them into one bool)
+      .def("batch_get_prepared_statuses",
+           [](GpuClient& g, DevGetBatch& b, bool verify) {
+             py::gil_scoped_release rel;
+             return unwrap(g.batch_get_device(b.items, verify, &b.session));
+           }, py::arg("batch"), py::arg("verify") = false)
       .def_property_readonly("session_put_steps", &GpuClient::session_put_steps)
       .def_property_readonly("striped_fused_items",
                              &GpuClient::striped_fused_items)
@@ -544,6 +580,7 @@ void bind_store(py::module_& m) {
   // (host-only logic, bound so the CPU suite can pin its invariants)
   using PC = PlacementCache;
   using EntryTuple = std::tuple<std::string, uint64_t, uint64_t, uint64_t>;
+  using ShardTuple = std::tuple<std::string, uint64_t, uint64_t>;
   static const auto entry_tuple = [](const PC::Entry& e) {
     return EntryTuple{e.pool_id, e.offset, e.size, e.digest};
   };
@@ -577,11 +614,46 @@ void bind_store(py::module_& m) {
         std::vector<PC::Put> ps;
         for (const auto& [k, e] : puts)
           ps.push_back({k, {std::get<0>(e), std::get<1>(e), std::get<2>(e),
-                            std::get<3>(e)}});
+                            std::get<3>(e), {}}});
         if (!bind_keys) return c.record(ps);
         const auto keys = key_list(*bind_keys);
         return c.record(ps, &keys);
       }, py::arg("puts"), py::arg("bind_keys") = py::none())
+      // a striped put: (key, size, digest, [(pool, offset, length)]) — the
+      // shard list of copy 0
+      .def("record_striped", [](PC& c,
+                                const std::vector<std::tuple<
+                                    std::string, uint64_t, uint64_t,
+                                    std::vector<ShardTuple>>>& puts,
+                                const std::optional<std::vector<std::string>>& bind_keys) {
+        std::vector<PC::Put> ps;
+        for (const auto& [k, size, digest, shards] : puts) {
+          PC::Entry e;
+          e.size = size;
+          e.digest = digest;
+          for (const auto& [pool, off, len] : shards)
+            e.shards.push_back({pool, off, len});
+          if (!e.shards.empty()) {
+            e.pool_id = e.shards[0].pool_id;
+            e.offset = e.shards[0].offset;
+          }
+          ps.push_back({k, std::move(e)});
+        }
+        if (!bind_keys) return c.record(ps);
+        const auto keys = key_list(*bind_keys);
+        return c.record(ps, &keys);
+      }, py::arg("puts"), py::arg("bind_keys") = py::none())
+      // the shard list of a cached key: [] for a single-range entry, None
+      // for an absent key
+      .def("find_shards", [](const PC& c, const std::string& key)
+               -> std::optional<std::vector<ShardTuple>> {
+        auto e = c.find(key);
+        if (!e) return std::nullopt;
+        std::vector<ShardTuple> out;
+        for (const auto& s : e->shards)
+          out.emplace_back(s.pool_id, s.offset, s.length);
+        return out;
+      })
       .def("erase", [](PC& c, const std::vector<std::string>& keys) {
         c.erase(key_list(keys));
       })

@@ -130,6 +130,66 @@ Result<CommitToken> decode_commit_token(const std::string& body) {
   return c;
 }
 
+std::string encode_session_open_response(uint64_t token) {
+  return encode_upsert_start(token);  // both are one u64
+}
+
+std::string encode_commit_token_shards(uint64_t token, bool release,
+                                       const uint64_t* obj_digests, size_t n,
+                                       const uint64_t* shard_digests,
+                                       size_t m) {
+  serde::Enc e;
+  e.num<uint64_t>(token);
+  e.num<uint8_t>(release ? 1 : 0);
+  e.num<uint32_t>(static_cast<uint32_t>(n));
+  for (size_t i = 0; i < n; ++i) e.num<uint64_t>(obj_digests[i]);
+  e.num<uint32_t>(static_cast<uint32_t>(m));
+  for (size_t i = 0; i < m; ++i) e.num<uint64_t>(shard_digests[i]);
+  return std::move(e.buf);
+}
+
+Result<SessionOpen> decode_session_open(const std::string& body) {
+  serde::Dec d(body.data(), body.size());
+  SessionOpen r;
+  const uint32_t count = d.num<uint32_t>();
+  if (!count_fits(count, d)) return bad("bad session open request");
+  r.keys.resize(count);
+  r.sizes.resize(count);
+  for (uint32_t i = 0; i < count && d.ok(); ++i) {
+    r.keys[i] = d.str();
+    r.sizes[i] = d.num<uint64_t>();
+  }
+  r.flags = d.num<uint8_t>();
+  if (!d.ok() || d.remaining() != 0) return bad("bad session open request");
+  return r;
+}
+
+Result<uint64_t> decode_session_open_response(const std::string& body) {
+  serde::Dec d(body.data(), body.size());
+  const uint64_t token = d.num<uint64_t>();
+  if (!d.ok()) return bad("bad session open response");
+  return token;
+}
+
+Result<CommitTokenShards> decode_commit_token_shards(const std::string& body) {
+  serde::Dec d(body.data(), body.size());
+  CommitTokenShards c;
+  c.token = d.num<uint64_t>();
+  c.flags = d.num<uint8_t>();
+  // each list is sized only once the body is known to hold it
+  auto list = [&d](std::vector<uint64_t>& out) {
+    const uint32_t n = d.num<uint32_t>();
+    if (!d.ok() || n > (1u << 24) || d.remaining() < n * sizeof(uint64_t))
+      return false;
+    out.resize(n);
+    for (auto& v : out) v = d.num<uint64_t>();
+    return true;
+  };
+  if (!list(c.obj_digests) || !list(c.shard_digests) || d.remaining() != 0)
+    return bad("bad shard commit request");
+  return c;
+}
+
 void append_item(BatchPlacements& out, PoolTable& table, int32_t status,
                  const std::vector<CopyPlacement>& copies, uint64_t size,
                  uint64_t checksum) {

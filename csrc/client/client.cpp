@@ -516,6 +516,34 @@ Result<void> Client::commit_by_token(uint64_t token, bool release,
   return {};
 }
 
+Result<void> Client::commit_by_token_shards(uint64_t token, bool release,
+                                            const uint64_t* obj_digests,
+                                            size_t n,
+                                            const uint64_t* shard_digests,
+                                            size_t m) {
+  auto r = meta_call_raw(M::BATCH_COMMIT_TOKEN_SHARDS,
+                         wire::encode_commit_token_shards(
+                             token, release, obj_digests, n, shard_digests, m));
+  if (!r.ok()) return r.error();
+  return {};
+}
+
+Result<uint64_t> Client::open_session(
+    const std::vector<std::pair<ObjectKey, uint64_t>>& objects,
+    bool allow_striped) {
+  struct Item {
+    const ObjectKey& key;
+    uint64_t size;
+  };
+  std::vector<Item> items;
+  items.reserve(objects.size());
+  for (const auto& [key, size] : objects) items.push_back({key, size});
+  auto r = meta_call_raw(M::BATCH_SESSION_OPEN,
+                         wire::encode_session_open(items, allow_striped));
+  if (!r.ok()) return r.error();
+  return wire::decode_session_open_response(r.value());
+}
+
 Result<void> Client::complete_by_keys(
     const std::vector<PutCompleteRequest>& reqs,
     const std::vector<uint32_t>& order, std::vector<int32_t>* statuses) {

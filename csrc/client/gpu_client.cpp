@@ -311,11 +311,9 @@ struct GpuClient::Router {
 // shard lengths and every shard resolves to a 16B-aligned device pointer;
 // the caller routes everything else the general way.
 struct GpuClient::StripeBatch {
-  struct Entry {
-    uint32_t item;
-    uint32_t first_obj, ncopies;  // kernel objects [first_obj, +ncopies)
-    uint32_t first_seg;           // segments of copy 0, copy 1, … back to back
-  };
+  using Entry = StripeRange;
+  template <bool Put>
+  using User = std::conditional_t<Put, const uint8_t*, uint8_t*>;
   std::vector<gpu::StripeSeg> segs;
   std::vector<uint64_t> obj_sizes;
   std::vector<Entry> entries;
@@ -325,17 +323,37 @@ struct GpuClient::StripeBatch {
   // bytes back to back (Put: the source; get: the destination). false =
   // not fusable, nothing added.
   template <bool Put>
-  bool add_copy(GpuClient& g, std::conditional_t<Put, const uint8_t*, uint8_t*> user,
-                uint64_t size, const CopyPlacement& copy) {
+  bool add_copy(GpuClient& g, User<Put> user, uint64_t size,
+                const CopyPlacement& copy) {
+    return add_shards<Put>(
+        user, size, copy.shards.size(),
+        [&](size_t k) { return copy.shards[k].length; },
+        [&](size_t k) { return g.resolve_device_ptr(copy.shards[k]); });
+  }
+  // The same from a striped placement-cache entry (copy 0 as recorded).
+  template <bool Put>
+  bool add_cached(GpuClient& g, User<Put> user,
+                  const PlacementCache::Entry& e) {
+    return add_shards<Put>(
+        user, e.size, e.shards.size(),
+        [&](size_t k) { return e.shards[k].length; },
+        [&](size_t k) -> uint8_t* {
+          uint8_t* base = g.resolve_pool_base(e.shards[k].pool_id);
+          return base ? base + e.shards[k].offset : nullptr;
+        });
+  }
+  template <bool Put, typename LenOf, typename PtrOf>
+  bool add_shards(User<Put> user, uint64_t size, size_t nshards, LenOf len_of,
+                  PtrOf ptr_of) {
     std::vector<uint64_t> lens;
-    lens.reserve(copy.shards.size());
-    for (const auto& s : copy.shards) lens.push_back(s.length);
+    lens.reserve(nshards);
+    for (size_t k = 0; k < nshards; ++k) lens.push_back(len_of(k));
     const auto plan = gpu::plan_stripe(size, lens);
     if (!plan) return false;
     const size_t mark = segs.size();
     const uint32_t obj = static_cast<uint32_t>(obj_sizes.size());
     for (size_t k = 0; k < plan->size(); ++k) {
-      uint8_t* pool_ptr = g.resolve_device_ptr(copy.shards[k]);
+      uint8_t* pool_ptr = ptr_of(k);
       if (!pool_ptr || !aligned16(pool_ptr, user + (*plan)[k].offset)) {
         segs.resize(mark);
         return false;
@@ -652,11 +670,44 @@ Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests) {
                         streams_[2]);
 }
 
+Result<void> GpuClient::session_stripe_kernel(SessionCore& sess,
+                                              uint64_t* seg_digests,
+                                              uint64_t* obj_digests) {
+  static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
+  const uint32_t nseg = static_cast<uint32_t>(sess.segs.size());
+  const uint32_t nobj = static_cast<uint32_t>(sess.obj_sizes.size());
+  if (!no_graph && !sess.stripe_plan && !sess.plan_failed) {
+    auto plan = std::make_shared<gpu::FusedStripePlan>();
+    auto rb = plan->build(sess.segs.data(), nseg, sess.obj_sizes.data(), nobj,
+                          device_);
+    if (rb.ok()) {
+      sess.stripe_plan = std::move(plan);
+    } else {
+      sess.plan_failed = true;  // capture unsupported: launch path
+      (void)hipGetLastError();   // clear any sticky launch error
+      BB_LOG(WARN) << "striped session graph capture unavailable ("
+                   << rb.error().message << "); using per-op launches";
+    }
+  }
+  if (sess.stripe_plan) {
+    auto r = sess.stripe_plan->run(seg_digests, obj_digests);
+    if (r.ok()) {
+      session_graph_steps_.fetch_add(1);
+      return r;
+    }
+    sess.stripe_plan.reset();  // replay failed: fall through to launches
+    sess.plan_failed = true;
+  }
+  return gpu::fused_stripe(sess.segs.data(), nseg, sess.obj_sizes.data(), nobj,
+                           seg_digests, obj_digests, streams_[2]);
+}
+
 // Token fast path: placements unchanged since last step ⇒ two tiny RPCs
 // bracket ONE fused copy+digest kernel launch. Returns nullopt when the
 // session is not usable (caller runs the full path, which re-establishes it).
 std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
     const std::vector<DevPutItem>& items, BatchPutSession* sess) {
+  if (sess && sess->striped()) return std::nullopt;  // the v1 path's session
   const uint32_t dpi = sess ? std::max<uint32_t>(sess->descs_per_item, 1) : 1;
   if (!sess || sess->token == 0 || !cache_.owns(sess->binding) ||
       items.empty() || sess->descs.size() != items.size() * dpi)
@@ -702,6 +753,111 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
   (void)cache_.refresh_digests(sess->binding, digests.data(), dpi);
   session_put_steps_.fetch_add(1);
   return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
+}
+
+// A striped session's segments still describe `items`: item i owns the
+// segments from its range to the next one's, each a slice of the item's
+// buffer (user_of(seg) == ptr + first_tile tiles) of an object whose size
+// fits size_ok(i, size).
+template <typename Item, typename UserOf, typename SizeOk>
+static bool stripe_session_matches(const GpuClient::SessionCore& s,
+                                   const std::vector<Item>& items,
+                                   UserOf user_of, SizeOk size_ok) {
+  if (s.ranges.size() != items.size()) return false;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const auto& r = s.ranges[i];
+    const size_t seg_end =
+        i + 1 < items.size() ? s.ranges[i + 1].first_seg : s.segs.size();
+    for (uint32_t c = 0; c < r.ncopies; ++c)
+      if (!size_ok(i, s.obj_sizes[r.first_obj + c])) return false;
+    for (size_t k = r.first_seg; k < seg_end; ++k) {
+      const gpu::StripeSeg& seg = s.segs[k];
+      if (seg.obj < r.first_obj || seg.obj >= r.first_obj + r.ncopies ||
+          user_of(seg) != static_cast<const uint8_t*>(items[i].ptr) +
+                              seg.first_tile * digest::kTileBytes)
+        return false;
+    }
+  }
+  return true;
+}
+
+// The striped put step: the same two RPCs around one FusedStripePlan replay;
+// the commit carries the object digests and every shard's own.
+std::optional<Result<std::vector<int32_t>>> GpuClient::try_striped_session_put(
+    const std::vector<DevPutItem>& items, BatchPutSession* sess) {
+  if (!sess || !sess->striped() || sess->token == 0 ||
+      !cache_.owns(sess->binding) || items.empty())
+    return std::nullopt;
+  if (!cache_.valid(sess->binding) ||
+      !stripe_session_matches(
+          *sess, items, [](const gpu::StripeSeg& s) { return s.src; },
+          [&](size_t i, uint64_t size) { return size == items[i].size; })) {
+    sess->token = 0;
+    return std::nullopt;
+  }
+  BB_TRACE_SCOPE("bb::session_put_striped");
+  // PENDING pins the placements before the one-sided writes (see
+  // try_session_put)
+  auto r1 = c_.meta_call_raw(M::BATCH_UPSERT_START,
+                             wire::encode_upsert_start(sess->token));
+  if (!r1.ok()) {
+    sess->token = 0;  // stale/error before any write: clean fallback
+    return std::nullopt;
+  }
+  std::vector<uint64_t> seg_digests(sess->segs.size(), 0);
+  std::vector<uint64_t> obj_digests(sess->obj_sizes.size(), 0);
+  auto rk = session_stripe_kernel(*sess, seg_digests.data(), obj_digests.data());
+  if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
+  // one digest per ITEM: copy 0's. A replica that disagrees saw the source
+  // change mid-step and must not commit — as on the one-shot path its item
+  // fails and is cancelled; the others commit by key, and the session ends.
+  std::vector<uint64_t> digests(items.size());
+  std::vector<int32_t> statuses(items.size(), 0);
+  bool agree = true;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const auto& r = sess->ranges[i];
+    digests[i] = obj_digests[r.first_obj];
+    for (uint32_t c = 1; c < r.ncopies; ++c)
+      if (obj_digests[r.first_obj + c] != digests[i]) {
+        statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
+        agree = false;
+      }
+  }
+  if (!agree) {
+    sess->token = 0;
+    std::vector<PutCompleteRequest> reqs;
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < items.size(); ++i) {
+      if (statuses[i] != 0) continue;
+      const auto& r = sess->ranges[i];
+      const size_t seg_end =
+          i + 1 < items.size() ? sess->ranges[i + 1].first_seg : sess->segs.size();
+      PutCompleteRequest pc{items[i].key, digests[i], {}};
+      pc.shard_digests.resize(r.ncopies);
+      for (size_t k = r.first_seg; k < seg_end; ++k)
+        pc.shard_digests[sess->segs[k].obj - r.first_obj].push_back(
+            seg_digests[k]);
+      reqs.push_back(std::move(pc));
+      order.push_back(static_cast<uint32_t>(i));
+    }
+    if (auto r = c_.complete_by_keys(reqs, order, &statuses); !r.ok())
+      return {r.error()};
+    cancel_failed(items, statuses);
+    return {Result<std::vector<int32_t>>(std::move(statuses))};
+  }
+  // segments lie in item, copy, shard order: the wire order of the digests
+  auto r2 = c_.commit_by_token_shards(sess->token, /*release=*/false,
+                                      digests.data(), digests.size(),
+                                      seg_digests.data(), seg_digests.size());
+  if (!r2.ok()) {
+    // placements changed mid-step (rare): the full path re-places and
+    // rewrites the batch
+    sess->token = 0;
+    return std::nullopt;
+  }
+  (void)cache_.refresh_digests(sess->binding, digests.data());
+  session_put_steps_.fetch_add(1);
+  return {Result<std::vector<int32_t>>(std::move(statuses))};
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
@@ -844,6 +1000,7 @@ Result<void> GpuClient::refetch(const std::vector<DevGetItem>& items,
 // previous step; a step is ONE kernel launch + digest compares, zero RPCs.
 std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     const std::vector<DevGetItem>& items, BatchGetSession* sess) {
+  if (sess && sess->striped()) return try_striped_session_get(items, sess);
   if (!sess || !sess->complete || !cache_.owns(sess->binding) ||
       sess->descs.size() != items.size() || items.empty())
     return std::nullopt;
@@ -881,6 +1038,48 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
   return {Result<std::vector<int32_t>>(std::move(statuses))};
 }
 
+// The striped get step: one FusedStripePlan replay gathers every shard into
+// the user buffers; the object digests are compared with the cached ones.
+std::optional<Result<std::vector<int32_t>>> GpuClient::try_striped_session_get(
+    const std::vector<DevGetItem>& items, BatchGetSession* sess) {
+  if (!sess->complete || !cache_.owns(sess->binding) || items.empty())
+    return std::nullopt;
+  std::vector<uint64_t> want(items.size());
+  if (sess->ranges.size() != items.size() ||
+      !cache_.read_digests(sess->binding, want.data(), want.size()) ||
+      !stripe_session_matches(
+          *sess, items,
+          [](const gpu::StripeSeg& s) {
+            return static_cast<const void*>(s.dst);
+          },
+          [&](size_t i, uint64_t size) { return size <= items[i].capacity; })) {
+    sess->complete = false;
+    return std::nullopt;
+  }
+  BB_TRACE_SCOPE("bb::session_get_striped");
+  std::vector<uint64_t> seg_got(sess->segs.size(), 0);
+  std::vector<uint64_t> got(sess->obj_sizes.size(), 0);
+  auto rk = session_stripe_kernel(*sess, seg_got.data(), got.data());
+  if (!rk.ok()) return {rk.error()};
+  std::vector<uint32_t> miss;
+  for (size_t j = 0; j < items.size(); ++j)
+    if (got[sess->ranges[j].first_obj] != want[j])
+      miss.push_back(static_cast<uint32_t>(j));
+  if (miss.empty()) {
+    session_get_steps_.fetch_add(1);
+    return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
+  }
+  // stale entries: as in try_session_get
+  PlacementCache::KeyList stale;
+  for (auto j : miss) stale.push_back(&items[j].key);
+  cache_.erase(stale);
+  sess->complete = false;
+  std::vector<int32_t> statuses(items.size(), 0);
+  if (auto r = refetch(items, miss, /*verify=*/true, statuses); !r.ok())
+    return {r.error()};
+  return {Result<std::vector<int32_t>>(std::move(statuses))};
+}
+
 Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
     const std::vector<DevGetItem>& items, bool verify, BatchGetSession* sess) {
   if (auto fast = try_session_get(items, sess)) return std::move(*fast);
@@ -898,7 +1097,22 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
   std::vector<gpu::PutDesc> descs;
   std::vector<uint32_t> hit_idx;
   std::vector<uint64_t> want;
+  StripeBatch stripes;  // hits on striped entries: verified by object digest
+  std::vector<uint64_t> stripe_want;
   for (const auto& [i, cp] : lk.hits) {
+    if (!cp.shards.empty()) {
+      if (fused_copy_ && aligned16(items[i].ptr) &&
+          stripes.add_cached<false>(*this, static_cast<uint8_t*>(items[i].ptr),
+                                    cp)) {
+        stripes.entries.push_back(
+            {i, static_cast<uint32_t>(stripes.obj_sizes.size() - 1), 1,
+             static_cast<uint32_t>(stripes.segs.size() - cp.shards.size())});
+        stripe_want.push_back(cp.digest);
+      } else {
+        miss_idx.push_back(i);
+      }
+      continue;
+    }
     uint8_t* base = resolve_pool_base(cp.pool_id);
     if (base && aligned16(items[i].ptr, base + cp.offset)) {
       descs.push_back(
@@ -910,24 +1124,39 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
     }
   }
   std::vector<int32_t> statuses(items.size(), 0);
-  if (!descs.empty()) {
+  if (!descs.empty() || !stripes.entries.empty()) {
     BB_TRACE_SCOPE("bb::cached_get");
     std::vector<uint64_t> got(descs.size(), 0);
     auto r = gpu::fused_put(descs.data(), static_cast<uint32_t>(descs.size()),
                             got.data(), streams_[2]);
     if (!r.ok()) return r.error();
+    BB_RETURN_IF_ERROR(stripes.run(streams_[2]));
+    striped_fused_get_items_.fetch_add(stripes.entries.size());
     PlacementCache::KeyList stale;
     for (size_t j = 0; j < hit_idx.size(); ++j)
       if (got[j] != want[j]) {
         stale.push_back(&items[hit_idx[j]].key);
         miss_idx.push_back(hit_idx[j]);  // refetch authoritatively
       }
-    // establish the get session when every item was a verified cache hit
-    // (desc j == item j) and no concurrent thread mutated the cache
-    auto binding = cache_.settle(std::move(lk), stale,
-                                 sess && hit_idx.size() == items.size());
+    for (size_t j = 0; j < stripes.entries.size(); ++j)
+      if (stripes.obj_digests[stripes.entries[j].first_obj] != stripe_want[j]) {
+        stale.push_back(&items[stripes.entries[j].item].key);
+        miss_idx.push_back(stripes.entries[j].item);
+      }
+    // establish the get session when every item was a verified cache hit of
+    // ONE kind (desc j == item j, or striped range j == item j; a mixed
+    // batch gets none) and no concurrent thread mutated the cache
+    const bool all_plain = hit_idx.size() == items.size();
+    const bool all_striped = stripes.entries.size() == items.size();
+    auto binding =
+        cache_.settle(std::move(lk), stale, sess && (all_plain || all_striped));
     if (binding.bound()) {
-      sess->rebind(std::move(descs), std::move(binding));
+      if (all_striped)
+        sess->rebind_striped(std::move(stripes.segs),
+                             std::move(stripes.obj_sizes),
+                             std::move(stripes.entries), std::move(binding));
+      else
+        sess->rebind(std::move(descs), std::move(binding));
       sess->complete = true;
     }
   }
@@ -1024,6 +1253,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
   if (cfg.max_workers_per_copy <= 1)
     return batch_put_device_v2(items, cfg, sess);
 
+  if (auto fast = try_striped_session_put(items, sess)) return std::move(*fast);
   BatchPutStartRequest breq;
   breq.requests.reserve(items.size());
   for (const auto& it : items)
@@ -1149,8 +1379,64 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
   }
   striped_fused_items_.fetch_add(stripes.entries.size());
 
-  BB_RETURN_IF_ERROR(complete_puts(items, rt, 1, &shard_digests, statuses,
-                                   /*apply_statuses=*/true));
+  // establish a striped session when EVERY item rode the fused_stripe launch
+  // (range j == item j). The server session is opened NOW: the objects are
+  // still PENDING, which pins the placements just resolved — after the
+  // commit a migration could make the session "current" over addresses this
+  // client no longer has right.
+  const bool all_striped = !items.empty() &&
+                           stripes.entries.size() == items.size() &&
+                           std::all_of(statuses.begin(), statuses.end(),
+                                       [](int32_t st) { return st == 0; });
+  uint64_t token = 0;
+  if (sess && cfg.replace && cfg.checksum && fused_copy_ && cache_.enabled() &&
+      all_striped) {
+    std::vector<std::pair<ObjectKey, uint64_t>> objects;
+    objects.reserve(items.size());
+    for (const auto& it : items) objects.emplace_back(it.key, it.size);
+    if (auto t = c_.open_session(objects, /*allow_striped=*/true); t.ok())
+      token = t.value();
+  }
+  // all striped: rt.plain_digests holds exactly the items' object digests,
+  // and the segments lie in item, copy, shard order — the wire order
+  const bool committed_by_token =
+      token != 0 &&
+      c_.commit_by_token_shards(token, /*release=*/false,
+                                rt.plain_digests.data(), items.size(),
+                                stripes.seg_digests.data(),
+                                stripes.seg_digests.size()).ok();
+  if (!committed_by_token)
+    BB_RETURN_IF_ERROR(complete_puts(items, rt, 1, &shard_digests, statuses,
+                                     /*apply_statuses=*/true));
+  if (!stripes.entries.empty() && cache_.enabled()) {
+    // remember copy 0 of every committed fused-striped item for RPC-free
+    // verified gets; with a session, bind it over all of them
+    std::vector<PlacementCache::Put> cached;
+    for (const auto& e : stripes.entries) {
+      if (statuses[e.item] != 0) continue;
+      const auto& shards = start->items[e.item].copies[0].shards;
+      PlacementCache::Entry ce{shards[0].pool_id, shards[0].offset,
+                               items[e.item].size,
+                               stripes.obj_digests[e.first_obj], {}};
+      for (const auto& s : shards)
+        ce.shards.push_back({s.pool_id, s.offset, s.length});
+      cached.push_back({items[e.item].key, std::move(ce)});
+    }
+    const bool bind = committed_by_token && cached.size() == items.size();
+    PlacementCache::KeyList keys;
+    if (bind)
+      for (const auto& p : cached) keys.push_back(&p.key);
+    auto binding = cache_.record(cached, bind ? &keys : nullptr);
+    if (bind) {
+      sess->token = binding.bound() ? token : 0;
+      if (binding.bound())
+        sess->rebind_striped(std::move(stripes.segs),
+                             std::move(stripes.obj_sizes),
+                             std::move(stripes.entries), std::move(binding));
+      else
+        sess->rebind({}, {});
+    }
+  }
   cancel_failed(items, statuses);
   return statuses;
 }
@@ -1249,7 +1535,8 @@ Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
   // (covers this client's own puts), metadata RPC as the general fallback
   ShuffleResolver resolve = [this](const ObjectKey& key,
                                    uint64_t size) -> const void* {
-    if (auto cp2 = cache_.find(key); cp2 && cp2->size == size) {
+    if (auto cp2 = cache_.find(key);
+        cp2 && cp2->size == size && cp2->shards.empty()) {
       // resolve_pool_base may RPC — the cache lock is not held here
       if (uint8_t* base = resolve_pool_base(cp2->pool_id))
         return base + cp2->offset;

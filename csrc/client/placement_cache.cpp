@@ -40,7 +40,7 @@ PlacementCache::Binding PlacementCache::record(const std::vector<Put>& puts,
     if (inserted) continue;
     Entry& e = it->second;
     if (e.pool_id != p.entry.pool_id || e.offset != p.entry.offset ||
-        e.size != p.entry.size)
+        e.size != p.entry.size || e.shards != p.entry.shards)
       ++epoch_;
     e = p.entry;
   }

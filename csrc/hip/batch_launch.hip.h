@@ -1,6 +1,8 @@
 // Host side of every batched launch: one block layout, one prefix sum, one
 // grid rule and one enqueue sequence, shared by checksum_batch, fused_put,
-// FusedPutPlan (digest.hip) and batched_copy (memops.hip).
+// FusedPutPlan (digest.hip) and batched_copy (memops.hip) — and the capture
+// scaffolding (GraphStep) under both session plans, FusedPutPlan and
+// FusedStripePlan (stripe.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,5 +95,71 @@ Result<void> enqueue_digest(void* device_block, uint32_t n, uint64_t total_tiles
                             stream));
   return {};
 }
+
+// A step captured once and replayed: what FusedPutPlan and FusedStripePlan
+// own and how they capture. The step's descriptors live in a device block
+// uploaded once; its digests land in a pinned buffer; capture and replay
+// happen on a dedicated non-blocking stream.
+struct GraphStep {
+  hipStream_t stream = nullptr;   // dedicated capture/replay stream
+  hipGraphExec_t exec = nullptr;
+  void* dev = nullptr;            // the uploaded block + its accumulators
+  uint64_t* h_out = nullptr;      // pinned digest landing zone
+  size_t out_bytes = 0;
+
+  GraphStep() = default;
+  GraphStep(const GraphStep&) = delete;
+  GraphStep& operator=(const GraphStep&) = delete;
+  ~GraphStep() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (dev) (void)hipFree(dev);
+    if (h_out) (void)hipHostFree(h_out);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+
+  // stream, device block of block_bytes with the first upload_bytes copied
+  // from h_block, pinned landing zone of out_bytes_
+  Result<void> prepare(const void* h_block, size_t upload_bytes,
+                       size_t block_bytes, size_t out_bytes_) {
+    out_bytes = out_bytes_;
+    BB_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    BB_HIP_TRY(hipMalloc(&dev, block_bytes));
+    BB_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), out_bytes,
+                             hipHostMallocDefault));
+    return copy_sync(dev, h_block, upload_bytes, hipMemcpyHostToDevice);
+  }
+
+  // Captures what enqueue(stream) issues and instantiates it.
+  template <typename Enqueue>
+  Result<void> capture(Enqueue&& enqueue) {
+    hipGraph_t graph = nullptr;
+    // Relaxed: every captured op is issued on `stream` by THIS thread, so
+    // the stricter modes buy nothing — and ROCm's ThreadLocal mode still
+    // fails OTHER threads' legacy-stream hipMemcpy while a capture is open
+    // ("operation would make the legacy stream depend on a capturing blocking
+    // stream"), which a concurrent client must be free to do.
+    BB_HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
+    // no early return while the capture is open: collect the error, end the
+    // capture, then report
+    const Result<void> cap = enqueue(stream);
+    hipError_t endc = hipStreamEndCapture(stream, &graph);
+    if (!cap.ok()) {
+      if (graph) (void)hipGraphDestroy(graph);
+      return Error{cap.code(), "graph capture: " + cap.message()};
+    }
+    BB_HIP_TRY(endc);
+    hipError_t inst = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    BB_HIP_TRY(inst);
+    return {};
+  }
+
+  // one graph launch; returns with the digests in h_out
+  Result<void> replay() {
+    BB_HIP_TRY(hipGraphLaunch(exec, stream));
+    BB_HIP_TRY(hipStreamSynchronize(stream));
+    return {};
+  }
+};
 
 }  // namespace blackbird::gpu

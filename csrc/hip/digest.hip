@@ -201,20 +201,7 @@ Result<void> fused_put(const PutDesc* descs, uint32_t n, uint64_t* out_digests,
 // are uploaded once and the step is captured as a graph: one hipGraphLaunch
 // replaces memset + 2 kernel launches + D2H issue each step.
 
-struct FusedPutPlan::Impl {
-  hipStream_t stream = nullptr;   // dedicated capture/replay stream
-  hipGraphExec_t exec = nullptr;
-  void* dev = nullptr;            // descs + prefix + out
-  uint64_t* h_out = nullptr;      // pinned digest landing zone
-  size_t out_bytes = 0;
-
-  ~Impl() {
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (dev) (void)hipFree(dev);
-    if (h_out) (void)hipHostFree(h_out);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
+struct FusedPutPlan::Impl : GraphStep {};
 
 FusedPutPlan::~FusedPutPlan() { delete impl_; }
 
@@ -224,40 +211,16 @@ Result<void> FusedPutPlan::build(const PutDesc* descs, uint32_t n, int device) {
   BB_HIP_TRY(hipSetDevice(device));
   auto impl = std::make_unique<Impl>();
   const BatchBlock b{n};
-  impl->out_bytes = b.out_bytes();
 
   auto h_block = std::make_unique<unsigned char[]>(b.upload_bytes());
   const uint64_t total = fill_block(b, h_block.get(), descs, kTileBytes);
   if (total == 0) return Error{ErrorCode::INVALID_ARGUMENT, "zero-byte batch"};
 
-  BB_HIP_TRY(hipStreamCreateWithFlags(&impl->stream, hipStreamNonBlocking));
-  BB_HIP_TRY(hipMalloc(&impl->dev, b.bytes()));
-  BB_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&impl->h_out),
-                           impl->out_bytes, hipHostMallocDefault));
-  BB_RETURN_IF_ERROR(copy_sync(impl->dev, h_block.get(), b.upload_bytes(),
-                               hipMemcpyHostToDevice));
-
-  hipGraph_t graph = nullptr;
-  // Relaxed: every captured op is issued on impl->stream by THIS thread, so
-  // the stricter modes buy nothing — and ROCm's ThreadLocal mode still
-  // fails OTHER threads' legacy-stream hipMemcpy while a capture is open
-  // ("operation would make the legacy stream depend on a capturing blocking
-  // stream"), which a concurrent client must be free to do.
-  BB_HIP_TRY(hipStreamBeginCapture(impl->stream,
-                                   hipStreamCaptureModeRelaxed));
-  // no early return while the capture is open: collect the error, end the
-  // capture, then report
-  const Result<void> cap =
-      enqueue_digest<true>(impl->dev, n, total, impl->h_out, impl->stream);
-  hipError_t endc = hipStreamEndCapture(impl->stream, &graph);
-  if (!cap.ok()) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return Error{cap.code(), "graph capture: " + cap.message()};
-  }
-  BB_HIP_TRY(endc);
-  hipError_t inst = hipGraphInstantiate(&impl->exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  BB_HIP_TRY(inst);
+  BB_RETURN_IF_ERROR(impl->prepare(h_block.get(), b.upload_bytes(), b.bytes(),
+                                   b.out_bytes()));
+  BB_RETURN_IF_ERROR(impl->capture([&](hipStream_t s) {
+    return enqueue_digest<true>(impl->dev, n, total, impl->h_out, s);
+  }));
   n_ = n;
   impl_ = impl.release();
   return {};
@@ -265,8 +228,7 @@ Result<void> FusedPutPlan::build(const PutDesc* descs, uint32_t n, int device) {
 
 Result<void> FusedPutPlan::run(uint64_t* out_digests) {
   if (!impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan not built"};
-  BB_HIP_TRY(hipGraphLaunch(impl_->exec, impl_->stream));
-  BB_HIP_TRY(hipStreamSynchronize(impl_->stream));
+  BB_RETURN_IF_ERROR(impl_->replay());
   std::memcpy(out_digests, impl_->h_out, impl_->out_bytes);
   return {};
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <memory>
 
 #include "batch_launch.hip.h"
 #include "blackbird/gpu/gpu_kernels.h"
@@ -63,6 +64,49 @@ __global__ void fused_stripe_finalize_kernel(
   else if (i - nseg < nobj) acc[i] = digest::finalize(acc[i], obj_sizes[i - nseg]);
 }
 
+// The host image of the uploaded part: segs, obj_sizes and the exclusive
+// prefix sum of the segments' tile counts. Returns the total tile count.
+uint64_t fill_stripe_block(const StripeBlock& b, void* host,
+                           const StripeSeg* segs, const uint64_t* obj_sizes) {
+  std::memcpy(b.segs(host), segs, b.nseg * sizeof(StripeSeg));
+  std::memcpy(b.obj_sizes(host), obj_sizes, b.nobj * sizeof(uint64_t));
+  uint64_t* h_prefix = b.prefix(host);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < b.nseg; ++i) {
+    h_prefix[i] = total;
+    total += (segs[i].nbytes + digest::kTileBytes - 1) / digest::kTileBytes;
+  }
+  return total;
+}
+
+// The striped step over an uploaded block: zero both accumulator arrays →
+// copy and hash every tile → finalize per segment and per object → both
+// digest arrays, {seg | obj}, to host_out (pinned). Only enqueues; the caller
+// synchronizes or captures `stream` (the twin of enqueue_digest).
+Result<void> enqueue_stripe(void* device_block, const StripeBlock& b,
+                            uint64_t total_tiles, uint64_t* host_out,
+                            hipStream_t stream) {
+  auto* d_seg_acc =
+      reinterpret_cast<unsigned long long*>(b.seg_acc(device_block));
+  auto* d_obj_acc =
+      reinterpret_cast<unsigned long long*>(b.obj_acc(device_block));
+  BB_HIP_TRY(hipMemsetAsync(d_seg_acc, 0, b.out_bytes(), stream));
+  if (total_tiles > 0) {
+    fused_stripe_kernel<<<digest_grid(total_tiles), kBlock, 0, stream>>>(
+        b.segs(device_block), b.prefix(device_block), b.nseg, total_tiles,
+        d_seg_acc, d_obj_acc);
+    BB_HIP_LAUNCHED("fused_stripe_kernel");
+  }
+  const uint32_t nout = b.nseg + b.nobj;
+  fused_stripe_finalize_kernel<<<(nout + 255) / 256, 256, 0, stream>>>(
+      b.segs(device_block), b.nseg, b.obj_sizes(device_block), b.nobj,
+      d_seg_acc);
+  BB_HIP_LAUNCHED("fused_stripe_finalize_kernel");
+  BB_HIP_TRY(hipMemcpyAsync(host_out, d_seg_acc, b.out_bytes(),
+                            hipMemcpyDeviceToHost, stream));
+  return {};
+}
+
 thread_local DescStaging g_stripe_stage;
 
 }  // namespace
@@ -83,35 +127,57 @@ Result<void> fused_stripe(const StripeSeg* segs, uint32_t nseg,
   void* host = g_stripe_stage.pinned;
   void* dev = g_stripe_stage.device;
 
-  std::memcpy(b.segs(host), segs, nseg * sizeof(StripeSeg));
-  std::memcpy(b.obj_sizes(host), obj_sizes, nobj * sizeof(uint64_t));
-  uint64_t* h_prefix = b.prefix(host);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < nseg; ++i) {
-    h_prefix[i] = total;
-    total += (segs[i].nbytes + digest::kTileBytes - 1) / digest::kTileBytes;
-  }
+  const uint64_t total = fill_stripe_block(b, host, segs, obj_sizes);
   BB_HIP_TRY(hipMemcpyAsync(dev, host, b.upload_bytes(), hipMemcpyHostToDevice,
                             stream));
-
-  auto* d_seg_acc = reinterpret_cast<unsigned long long*>(b.seg_acc(dev));
-  auto* d_obj_acc = reinterpret_cast<unsigned long long*>(b.obj_acc(dev));
-  BB_HIP_TRY(hipMemsetAsync(d_seg_acc, 0, b.out_bytes(), stream));
-  if (total > 0) {
-    fused_stripe_kernel<<<digest_grid(total), kBlock, 0, stream>>>(
-        b.segs(dev), b.prefix(dev), nseg, total, d_seg_acc, d_obj_acc);
-    BB_HIP_LAUNCHED("fused_stripe_kernel");
-  }
-  const uint32_t nout = nseg + nobj;
-  fused_stripe_finalize_kernel<<<(nout + 255) / 256, 256, 0, stream>>>(
-      b.segs(dev), nseg, b.obj_sizes(dev), nobj, d_seg_acc);
-  BB_HIP_LAUNCHED("fused_stripe_finalize_kernel");
   uint64_t* h_out = b.seg_acc(host);
-  BB_HIP_TRY(hipMemcpyAsync(h_out, d_seg_acc, b.out_bytes(),
-                            hipMemcpyDeviceToHost, stream));
+  BB_RETURN_IF_ERROR(enqueue_stripe(dev, b, total, h_out, stream));
   BB_HIP_TRY(hipStreamSynchronize(stream));
   std::memcpy(out_seg_digests, h_out, nseg * sizeof(uint64_t));
   std::memcpy(out_obj_digests, b.obj_acc(host), nobj * sizeof(uint64_t));
+  return {};
+}
+
+// -------------- hipGraph-replayed striped session step (FusedStripePlan) ----
+// The striped counterpart of FusedPutPlan: the block is uploaded once and the
+// step enqueue_stripe issues — accumulator reset included — is captured as
+// one chain and replayed with one hipGraphLaunch.
+
+struct FusedStripePlan::Impl : GraphStep {};
+
+FusedStripePlan::~FusedStripePlan() { delete impl_; }
+
+Result<void> FusedStripePlan::build(const StripeSeg* segs, uint32_t nseg,
+                                    const uint64_t* obj_sizes, uint32_t nobj,
+                                    int device) {
+  if (impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan already built"};
+  if (nseg == 0) return Error{ErrorCode::INVALID_ARGUMENT, "empty segment list"};
+  BB_RETURN_IF_ERROR(check_stripe_segs(segs, nseg, obj_sizes, nobj));
+  BB_HIP_TRY(hipSetDevice(device));
+  auto impl = std::make_unique<Impl>();
+  const StripeBlock b{nseg, nobj};
+
+  auto h_block = std::make_unique<unsigned char[]>(b.upload_bytes());
+  const uint64_t total = fill_stripe_block(b, h_block.get(), segs, obj_sizes);
+  if (total == 0) return Error{ErrorCode::INVALID_ARGUMENT, "zero-byte batch"};
+
+  BB_RETURN_IF_ERROR(impl->prepare(h_block.get(), b.upload_bytes(), b.bytes(),
+                                   b.out_bytes()));
+  BB_RETURN_IF_ERROR(impl->capture([&](hipStream_t s) {
+    return enqueue_stripe(impl->dev, b, total, impl->h_out, s);
+  }));
+  nseg_ = nseg;
+  nobj_ = nobj;
+  impl_ = impl.release();
+  return {};
+}
+
+Result<void> FusedStripePlan::run(uint64_t* out_seg_digests,
+                                  uint64_t* out_obj_digests) {
+  if (!impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan not built"};
+  BB_RETURN_IF_ERROR(impl_->replay());
+  std::memcpy(out_seg_digests, impl_->h_out, nseg_ * sizeof(uint64_t));
+  std::memcpy(out_obj_digests, impl_->h_out + nseg_, nobj_ * sizeof(uint64_t));
   return {};
 }
 

@@ -1,7 +1,8 @@
 // Wire codec of the compact v2 batch protocol: BATCH_PUT_START2,
-// BATCH_GET_WORKERS2, BATCH_UPSERT_START and BATCH_COMMIT_TOKEN. Clients and
-// the keystone handlers both go through these functions; nothing else spells
-// the layouts out.
+// BATCH_GET_WORKERS2, BATCH_UPSERT_START and BATCH_COMMIT_TOKEN, and of the
+// two session messages that serve striped copies, BATCH_SESSION_OPEN and
+// BATCH_COMMIT_TOKEN_SHARDS. Clients and the keystone handlers both go
+// through these functions; nothing else spells the layouts out.
 //
 //   BATCH_PUT_START2 request
 //     u32 count | u64 uniform_size (0 = per-item sizes follow) |
@@ -18,6 +19,13 @@
 //       u8 1, i32 status   (NOT_IMPLEMENTED = striped object: use v1)
 //   BATCH_UPSERT_START   u64 token
 //   BATCH_COMMIT_TOKEN   u64 token | u8 flags (bit 0: release) | u32 n | u64*n
+//   BATCH_SESSION_OPEN request
+//     u32 count | {str key, u64 size}*count | u8 flags (bit 0: allow striped)
+//   BATCH_SESSION_OPEN response
+//     u64 token (0 = refused)
+//   BATCH_COMMIT_TOKEN_SHARDS
+//     u64 token | u8 flags (bit 0: release) | u32 n | u64*n | u32 m | u64*m
+//     (n object digests; m shard digests in object, copy, shard order)
 //   pool table           u16 npools | str pool_id * npools
 //
 // The responses carry no item count (the caller knows how many it asked for).
@@ -75,6 +83,19 @@ struct CommitToken {
   std::vector<uint64_t> digests;
 };
 
+struct SessionOpen {
+  std::vector<ObjectKey> keys;
+  std::vector<uint64_t> sizes;
+  uint8_t flags = 0;  // bit 0: striped copies may join
+};
+
+struct CommitTokenShards {
+  uint64_t token = 0;
+  uint8_t flags = 0;  // bit 0: release the session after the commit
+  std::vector<uint64_t> obj_digests;
+  std::vector<uint64_t> shard_digests;  // object, copy, shard order
+};
+
 // ---- requests (clients encode; items are keys or structs with .key/.size)
 template <typename T>
 const ObjectKey& key_of(const T& item) {
@@ -116,12 +137,32 @@ std::string encode_commit_token(uint64_t token, bool release,
                                 const uint64_t* digests, size_t n,
                                 size_t stride = 1);
 
+template <typename Item>
+std::string encode_session_open(const std::vector<Item>& items,
+                                bool allow_striped) {
+  serde::Enc e;
+  e.num<uint32_t>(static_cast<uint32_t>(items.size()));
+  for (auto& it : items) {
+    e.str(it.key);
+    e.num<uint64_t>(it.size);
+  }
+  e.num<uint8_t>(allow_striped ? 1 : 0);
+  return std::move(e.buf);
+}
+std::string encode_session_open_response(uint64_t token);
+std::string encode_commit_token_shards(uint64_t token, bool release,
+                                       const uint64_t* obj_digests, size_t n,
+                                       const uint64_t* shard_digests, size_t m);
+
 // ---- requests (keystone decodes); PROTOCOL_ERROR on a malformed body
 Result<PutStart2Request> decode_put_start2_request(const std::string& body);
 Result<std::vector<ObjectKey>> decode_get_workers2_request(
     const std::string& body);
 Result<uint64_t> decode_upsert_start(const std::string& body);
 Result<CommitToken> decode_commit_token(const std::string& body);
+Result<SessionOpen> decode_session_open(const std::string& body);
+Result<uint64_t> decode_session_open_response(const std::string& body);
+Result<CommitTokenShards> decode_commit_token_shards(const std::string& body);
 
 // ---- responses
 // Pool table under construction: interns pool ids in first-seen order.

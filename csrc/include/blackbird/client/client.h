@@ -129,6 +129,17 @@ class Client {
       st.value()[redo_idx[j]] = std::move(st2.value()[j]);
     return st;
   }
+  // ---- sessions over striped copies (GpuClient's striped fast path) ----
+  // BATCH_SESSION_OPEN for objects this client holds PENDING (between its
+  // BATCH_PUT_START and the commit): {key, size} pairs; token 0 = refused.
+  Result<uint64_t> open_session(
+      const std::vector<std::pair<ObjectKey, uint64_t>>& objects,
+      bool allow_striped);
+  // BATCH_COMMIT_TOKEN_SHARDS: n object digests and every shard's own, in
+  // object, copy, shard order
+  Result<void> commit_by_token_shards(uint64_t token, bool release,
+                                      const uint64_t* obj_digests, size_t n,
+                                      const uint64_t* shard_digests, size_t m);
   // steps served by the host session fast path (tests/bench introspection)
   uint64_t host_session_steps() const { return host_session_steps_.load(); }
 

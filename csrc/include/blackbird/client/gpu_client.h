@@ -65,6 +65,16 @@ class GpuClient {
   // re-validated each step. Requires replace=true, checksum=true
   // and the placement cache enabled; replicated placements are supported
   // (one destination per copy).
+  // Striped placements (max_workers_per_copy > 1) have the same three fast
+  // paths when every item of the batch rides the fused_stripe launch (each
+  // copy accepted by gpu::plan_stripe, every shard a 16B-aligned
+  // device-visible pointer): the session then carries the segment list
+  // instead of descs, a step replays a FusedStripePlan, and a put step
+  // commits the object digests together with every shard's own
+  // (BATCH_COMMIT_TOKEN_SHARDS). The server session is opened with
+  // BATCH_SESSION_OPEN between BATCH_PUT_START and the commit, while PENDING
+  // pins the placements just resolved. A session is either all single-shard
+  // or all striped; a batch with one item on another route gets none.
   // A session's hold on the placement cache is a PlacementCache::Binding:
   // the cache that issued it refuses it once any placement was erased,
   // moved or cleared, so a step never reaches a dead cache entry.
@@ -75,9 +85,22 @@ class GpuClient {
   // mismatch → RPC fallback; an EMBEDDED worker that frees its pool
   // in-process can fault — stop in-process workers only after their
   // clients.
+  // Where one item's kernel objects and segments sit in a striped launch.
+  struct StripeRange {
+    uint32_t item;
+    uint32_t first_obj, ncopies;  // kernel objects [first_obj, +ncopies)
+    uint32_t first_seg;           // segments of copy 0, copy 1, … back to back
+  };
   struct SessionCore {
     PlacementCache::Binding binding;  // the items' digest slots, item order
     std::vector<gpu::PutDesc> descs;  // user buffer ↔ pool range
+    // striped form (descs empty): the fused_stripe argument lists and each
+    // item's range into them, item order
+    std::vector<gpu::StripeSeg> segs;
+    std::vector<uint64_t> obj_sizes;
+    std::vector<StripeRange> ranges;
+    std::shared_ptr<gpu::FusedStripePlan> stripe_plan;  // lazily built too
+    bool striped() const { return !segs.empty(); }
     // hipGraph replay of the step (descs fixed ⇒ captured once, one graph
     // launch per step); built lazily on the first session step
     std::shared_ptr<gpu::FusedPutPlan> plan;
@@ -85,8 +108,26 @@ class GpuClient {
     // a new desc list: a kept plan would replay the old one
     void rebind(std::vector<gpu::PutDesc> d, PlacementCache::Binding b) {
       descs = std::move(d);
+      segs.clear();
+      obj_sizes.clear();
+      ranges.clear();
+      reset(std::move(b));
+    }
+    void rebind_striped(std::vector<gpu::StripeSeg> s,
+                        std::vector<uint64_t> sizes,
+                        std::vector<StripeRange> r, PlacementCache::Binding b) {
+      descs.clear();
+      segs = std::move(s);
+      obj_sizes = std::move(sizes);
+      ranges = std::move(r);
+      reset(std::move(b));
+    }
+
+   private:
+    void reset(PlacementCache::Binding b) {
       binding = std::move(b);
       plan.reset();
+      stripe_plan.reset();
       plan_failed = false;
     }
   };
@@ -259,6 +300,15 @@ class GpuClient {
   // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
   // or a failed capture pins the session to the launch path)
   Result<void> session_kernel(SessionCore& sess, uint64_t* digests);
+  // the same over a striped session's segment list (FusedStripePlan replay,
+  // fused_stripe launches otherwise)
+  Result<void> session_stripe_kernel(SessionCore& sess, uint64_t* seg_digests,
+                                     uint64_t* obj_digests);
+  // the striped forms of the two session steps
+  std::optional<Result<std::vector<int32_t>>> try_striped_session_put(
+      const std::vector<DevPutItem>& items, BatchPutSession* sess);
+  std::optional<Result<std::vector<int32_t>>> try_striped_session_get(
+      const std::vector<DevGetItem>& items, BatchGetSession* sess);
   bool fused_copy_ = true;
   bool initialized_ = false;
 };

@@ -1,5 +1,6 @@
 // Verified placement cache: {pool, offset, size, digest} of this client's own
-// puts, by key, plus the session bindings that ride on it.
+// puts, by key — for a striped object the shard list of copy 0 as well — plus
+// the session bindings that ride on it.
 //
 // The class owns the map, its lock, the enabled flag and the invalidation
 // epoch. A Binding is a session's hold on the digest slots of an ordered key
@@ -27,11 +28,24 @@ class PlacementCache {
   // past this many entries a put batch empties the cache (bindings die)
   static constexpr size_t kMaxEntries = size_t{1} << 20;
 
+  // One shard of a striped copy: the object's bytes lie in the shards back
+  // to back.
+  struct Shard {
+    PoolId pool_id;
+    uint64_t offset = 0;
+    uint64_t length = 0;
+    bool operator==(const Shard& o) const {
+      return pool_id == o.pool_id && offset == o.offset && length == o.length;
+    }
+  };
   struct Entry {
     PoolId pool_id;
     uint64_t offset = 0;
     uint64_t size = 0;
-    uint64_t digest = 0;
+    uint64_t digest = 0;  // of the whole object, striped or not
+    // copy 0 of a striped object; empty = the single range above (a striped
+    // entry keeps shard 0's pool and offset there)
+    std::vector<Shard> shards;
   };
   // key lists point at strings the caller keeps alive for the call
   using KeyList = std::vector<const ObjectKey*>;
@@ -61,8 +75,8 @@ class PlacementCache {
   std::optional<Entry> find(const ObjectKey& key) const;
 
   // One put batch under one lock: a zero digest is skipped, a new key is
-  // inserted, a known key overwritten — and if its pool, offset or size
-  // changed (a re-placed object) every binding dies: sessions hold the old
+  // inserted, a known key overwritten — and if its pool, offset, size or
+  // shard list changed (a re-placed object) every binding dies: sessions hold the old
   // pool addresses. Growing past kMaxEntries empties the cache. With
   // `bind_keys` the result is a binding over those keys in order, unbound
   // if one is absent. A disabled cache records and binds nothing.

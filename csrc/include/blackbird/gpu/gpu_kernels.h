@@ -126,6 +126,31 @@ class FusedPutPlan {
   uint32_t n_ = 0;
 };
 
+// The same for a striped session (fixed segment list every step): build
+// checks the segments (check_stripe_segs) before any HIP call, uploads
+// {segs | prefix | obj_sizes} once and captures accumulator reset →
+// fused_stripe kernel → finalize → D2H of both digest arrays as one chain;
+// run() is one graph launch and blocks until out_seg_digests[nseg] and
+// out_obj_digests[nobj] are filled. size() is the segment count.
+class FusedStripePlan {
+ public:
+  FusedStripePlan() = default;
+  ~FusedStripePlan();
+  FusedStripePlan(const FusedStripePlan&) = delete;
+  FusedStripePlan& operator=(const FusedStripePlan&) = delete;
+
+  Result<void> build(const StripeSeg* segs, uint32_t nseg,
+                     const uint64_t* obj_sizes, uint32_t nobj, int device);
+  bool ready() const { return impl_ != nullptr; }
+  uint32_t size() const { return nseg_; }
+  Result<void> run(uint64_t* out_seg_digests, uint64_t* out_obj_digests);
+
+ private:
+  struct Impl;
+  Impl* impl_ = nullptr;
+  uint32_t nseg_ = 0, nobj_ = 0;
+};
+
 // Simple utilities used by tests/benchmarks.
 Result<void> fill_pattern(void* dev_ptr, uint64_t nbytes, uint64_t seed,
                           hipStream_t stream);

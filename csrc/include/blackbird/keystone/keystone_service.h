@@ -74,12 +74,34 @@ class KeystoneService {
   // SESSION_STALE — the client falls back to the full batch_put_start path.
   // No UCX analogue in the reference; its closest pattern is the batch RPC
   // loop at keystone_service.cpp:302-360.
-  uint64_t create_put_session(const std::vector<PutStartRequest>& reqs);
+  // Striped copies join only with allow_striped: the session then remembers
+  // every object's shard shape and commits through commit_token_shards.
+  // pending_only (BATCH_SESSION_OPEN): granted only if every object is
+  // PENDING with the size the request names — a client opens its session
+  // between BATCH_PUT_START and the commit, while PENDING pins the
+  // placements it just resolved.
+  uint64_t create_put_session(const std::vector<PutStartRequest>& reqs,
+                              bool allow_striped = false,
+                              bool pending_only = false);
+  // BATCH_SESSION_OPEN: create_put_session(pending_only) behind the leader
+  // check; token 0 = refused
+  Result<uint64_t> open_session(const std::vector<PutStartRequest>& reqs,
+                                bool allow_striped);
   Result<void> upsert_start_token(uint64_t token);
   // release=true erases the session after a successful commit (one-shot
   // token commits from cold batch puts — no key strings on the wire)
   Result<void> commit_token(uint64_t token, const std::vector<uint64_t>& digests,
                             bool release = false);
+  // The same commit with every shard's own digest: shard_digests in object,
+  // copy, shard order, one per shard the session held at creation. A wrong
+  // count of either list is INVALID_ARGUMENT with nothing applied. Serves
+  // single-shard sessions too (one digest per copy). commit_token refuses a
+  // session holding a striped copy: it would stamp the object digest on
+  // shard 0.
+  Result<void> commit_token_shards(uint64_t token,
+                                   const std::vector<uint64_t>& obj_digests,
+                                   const std::vector<uint64_t>& shard_digests,
+                                   bool release = false);
   uint64_t token_commits() const { return ctr_token_commits_.load(); }
 
   // ------------------------------------------------------ cluster view
@@ -215,14 +237,27 @@ class KeystoneService {
   struct PutSession {
     std::vector<ObjectMeta*> metas;
     std::vector<uint64_t> sizes;
+    // shard shape at creation: shards[shard_begin[i] .. shard_begin[i+1]) are
+    // the shard counts of object i's copies, in copy order
+    std::vector<uint32_t> shards;
+    std::vector<uint32_t> shard_begin;
+    size_t total_shards = 0;
+    bool striped = false;  // some copy has more than one shard
     uint64_t epoch = 0;
     uint64_t created_ms = 0;
   };
   uint64_t placement_epoch_ = 0;  // guarded by objects_mu_ (unique)
   void bump_placement_epoch_locked() { ++placement_epoch_; }
   std::shared_ptr<PutSession> find_session(uint64_t token);  // or null
-  // epoch and sizes still match; objects_mu_ held (shared suffices)
+  // epoch and sizes still match — and, for a session that holds a striped
+  // copy, every object's copy count and shard counts; objects_mu_ held
+  // (shared suffices)
   Result<void> session_current_locked(const PutSession& s) const;
+  // the body of both token commits; commit_one(meta, index, now) applies one
+  // object's transition
+  template <typename CommitOne>
+  Result<void> commit_session(uint64_t token, const PutSession& s, bool release,
+                              CommitOne commit_one);
   std::mutex sessions_mu_;
   std::unordered_map<uint64_t, std::shared_ptr<PutSession>> put_sessions_;
   std::atomic<uint64_t> next_session_token_{1};

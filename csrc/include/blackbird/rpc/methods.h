@@ -42,6 +42,11 @@ constexpr uint16_t ADMIN_COMPACT = 25;
 // re-sending every key both ways
 constexpr uint16_t BATCH_UPSERT_START = 26;
 constexpr uint16_t BATCH_COMMIT_TOKEN = 27;
+// sessions over striped copies: a client that resolved its placements with
+// BATCH_PUT_START opens the session while its objects are still PENDING, and
+// commits every step with the object digests AND each shard's own digest
+constexpr uint16_t BATCH_SESSION_OPEN = 28;
+constexpr uint16_t BATCH_COMMIT_TOKEN_SHARDS = 29;
 
 // worker data plane (TCP fallback path; SHM/HIP-IPC paths bypass RPC)
 constexpr uint16_t DATA_WRITE = 200;

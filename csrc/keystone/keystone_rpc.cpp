@@ -217,6 +217,24 @@ void KeystoneServer::register_handlers() {
     BB_RETURN_IF_ERROR(ks.commit_token(c->token, c->digests, c->flags & 1));
     return std::string{};
   });
+  on(M::BATCH_SESSION_OPEN, [&ks](const std::string& b, const Ctx&) -> Reply {
+    auto rq = wire::decode_session_open(b);
+    if (!rq.ok()) return rq.error();
+    std::vector<PutStartRequest> reqs;
+    reqs.reserve(rq->keys.size());
+    for (size_t i = 0; i < rq->keys.size(); ++i)
+      reqs.push_back({std::move(rq->keys[i]), rq->sizes[i], {}});
+    auto token = ks.open_session(reqs, rq->flags & 1);
+    if (!token.ok()) return token.error();
+    return wire::encode_session_open_response(token.value());
+  });
+  on(M::BATCH_COMMIT_TOKEN_SHARDS, [&ks](const std::string& b, const Ctx&) -> Reply {
+    auto c = wire::decode_commit_token_shards(b);
+    if (!c.ok()) return c.error();
+    BB_RETURN_IF_ERROR(ks.commit_token_shards(c->token, c->obj_digests,
+                                              c->shard_digests, c->flags & 1));
+    return std::string{};
+  });
   leader_only(M::BATCH_REMOVE, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();

@@ -625,26 +625,42 @@ std::vector<int32_t> KeystoneService::batch_remove(
 // ------------------------------------------------- sessionful upserts
 
 uint64_t KeystoneService::create_put_session(
-    const std::vector<PutStartRequest>& reqs) {
+    const std::vector<PutStartRequest>& reqs, bool allow_striped,
+    bool pending_only) {
   if (reqs.empty()) return 0;
   auto s = std::make_shared<PutSession>();
   s->metas.reserve(reqs.size());
   s->sizes.reserve(reqs.size());
+  s->shard_begin.reserve(reqs.size() + 1);
   s->created_ms = now_ms();
   {
     std::shared_lock lk(objects_mu_);
     for (const auto& r : reqs) {
       auto it = objects_.find(r.key);
-      // sessions cover single-SHARD copies (any replica count): the token
-      // commit records ONE digest per object — every replica holds the
-      // same bytes — and the client resolves one destination per copy
       if (it == objects_.end() || it->second.copies.empty())
         return 0;
-      for (const auto& c : it->second.copies)
-        if (c.shards.size() != 1) return 0;
+      const ObjectMeta& m = it->second;
+      if (pending_only &&
+          (m.size != r.size || rload(m.state) != ObjectState::PENDING))
+        return 0;
+      // without allow_striped sessions cover single-SHARD copies (any
+      // replica count): commit_token records ONE digest per object — every
+      // replica holds the same bytes — and the client resolves one
+      // destination per copy
+      s->shard_begin.push_back(static_cast<uint32_t>(s->shards.size()));
+      for (const auto& c : m.copies) {
+        if (c.shards.empty()) return 0;
+        if (c.shards.size() != 1) {
+          if (!allow_striped) return 0;
+          s->striped = true;
+        }
+        s->shards.push_back(static_cast<uint32_t>(c.shards.size()));
+        s->total_shards += c.shards.size();
+      }
       s->metas.push_back(&it->second);
-      s->sizes.push_back(it->second.size);
+      s->sizes.push_back(m.size);
     }
+    s->shard_begin.push_back(static_cast<uint32_t>(s->shards.size()));
     s->epoch = placement_epoch_;
   }
   uint64_t token = next_session_token_.fetch_add(1);
@@ -658,6 +674,12 @@ uint64_t KeystoneService::create_put_session(
     put_sessions_.erase(oldest);
   }
   return token;
+}
+
+Result<uint64_t> KeystoneService::open_session(
+    const std::vector<PutStartRequest>& reqs, bool allow_striped) {
+  if (!is_leader()) return not_leader();
+  return create_put_session(reqs, allow_striped, /*pending_only=*/true);
 }
 
 std::shared_ptr<KeystoneService::PutSession> KeystoneService::find_session(
@@ -677,6 +699,22 @@ Result<void> KeystoneService::session_current_locked(
   for (size_t i = 0; i < s.metas.size(); ++i)
     if (s.metas[i]->size != s.sizes[i])
       return Error{ErrorCode::SESSION_STALE, "object shape changed"};
+  // The shard shape sits in other cache lines of the object than its size
+  // (the copies vector, and the shard counts behind its heap array), read on
+  // both calls of every step: measured 2–4 % of a 4096 × 64 KiB single-shard
+  // session step. Only a session that holds a striped copy pays for it — its
+  // commit regroups a flat digest list by the remembered shape. An
+  // all-single-shard session stamps shard 0 of each copy, as it did before
+  // sessions could be striped.
+  if (!s.striped) return {};
+  for (size_t i = 0; i < s.metas.size(); ++i) {
+    const ObjectMeta& m = *s.metas[i];
+    const uint32_t* shape = s.shards.data() + s.shard_begin[i];
+    bool same = m.copies.size() == s.shard_begin[i + 1] - s.shard_begin[i];
+    for (size_t c = 0; same && c < m.copies.size(); ++c)
+      same = m.copies[c].shards.size() == shape[c];
+    if (!same) return Error{ErrorCode::SESSION_STALE, "object shape changed"};
+  }
   return {};
 }
 
@@ -705,18 +743,63 @@ Result<void> KeystoneService::commit_token(
   if (!s) return Error{ErrorCode::SESSION_STALE, "unknown put session"};
   if (digests.size() != s->metas.size())
     return Error{ErrorCode::INVALID_ARGUMENT, "digest count mismatch"};
+  if (s->striped)
+    return Error{ErrorCode::INVALID_ARGUMENT,
+                 "striped session commits with shard digests"};
+  return commit_session(token, *s, release, [&](ObjectMeta& m, size_t i,
+                                                uint64_t now) {
+    commit_meta(m, digests[i], now);
+  });
+}
+
+Result<void> KeystoneService::commit_token_shards(
+    uint64_t token, const std::vector<uint64_t>& obj_digests,
+    const std::vector<uint64_t>& shard_digests, bool release) {
+  if (!is_leader()) return not_leader();
+  auto s = find_session(token);
+  if (!s) return Error{ErrorCode::SESSION_STALE, "unknown put session"};
+  if (obj_digests.size() != s->metas.size())
+    return Error{ErrorCode::INVALID_ARGUMENT, "digest count mismatch"};
+  if (shard_digests.size() != s->total_shards)
+    return Error{ErrorCode::INVALID_ARGUMENT, "shard digest count mismatch"};
+  // the flat list regrouped per copy for the one commit transition; the
+  // session's shape was re-checked against the object by the time this runs
+  std::vector<std::vector<uint64_t>> sd;
+  size_t next = 0;
+  return commit_session(token, *s, release, [&](ObjectMeta& m, size_t i,
+                                                uint64_t now) {
+    const uint32_t ncopies = s->shard_begin[i + 1] - s->shard_begin[i];
+    sd.resize(ncopies);
+    for (uint32_t c = 0; c < ncopies; ++c) {
+      const uint32_t ns = s->shards[s->shard_begin[i] + c];
+      sd[c].assign(shard_digests.begin() + next,
+                   shard_digests.begin() + next + ns);
+      next += ns;
+    }
+    commit_meta(m, obj_digests[i], sd, now);
+  });
+}
+
+// What both token commits share once their arguments are counted: the epoch
+// check under the shared lock, one transition per object, dirty marking, the
+// view bump, the counter, the optional release and the flush.
+template <typename CommitOne>
+Result<void> KeystoneService::commit_session(uint64_t token,
+                                             const PutSession& s,
+                                             bool release,
+                                             CommitOne commit_one) {
   const uint64_t now = now_ms();
   // SHARED lock — see upsert_start_token
   std::shared_lock lk(objects_mu_);
-  BB_RETURN_IF_ERROR(session_current_locked(*s));
+  BB_RETURN_IF_ERROR(session_current_locked(s));
   const bool persist = config_.persist_objects;
-  const size_t n = s->metas.size();
+  const size_t n = s.metas.size();
   for (size_t i = 0; i < n; ++i) {
     // metas are scattered map nodes: prefetch ahead — this loop is in the
     // hot warm-step path (one commit per session put step)
-    if (i + 8 < n) __builtin_prefetch(s->metas[i + 8], 1, 1);
-    ObjectMeta* m = s->metas[i];
-    commit_meta(*m, digests[i], now);
+    if (i + 8 < n) __builtin_prefetch(s.metas[i + 8], 1, 1);
+    ObjectMeta* m = s.metas[i];
+    commit_one(*m, i, now);
     if (persist) mark_dirty_locked(m->key, false);
   }
   bump_view();
