@@ -15,6 +15,8 @@ static void usage() {
       "bbctl [--keystone H:P] <command> ...\n"
       "  put <key> <file|->      store a file (or stdin)\n"
       "  get <key> [file]        fetch an object (stdout by default)\n"
+      "      --range OFF:LEN     only these bytes (unverified)\n"
+      "  patch <key> <off> <file|->   overwrite bytes of an object in place\n"
       "  rm <key>                remove an object\n"
       "  exists <key>\n"
       "  stat                    cluster stats\n"
@@ -30,13 +32,25 @@ int main(int argc, char** argv) {
   ClientOptions opts;
   PlacementConfig pcfg;
   std::vector<std::string> args;
+  bool ranged = false;
+  uint64_t range_off = 0, range_len = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
     if (a == "--keystone") opts.keystone_endpoint = next();
     else if (a == "--replication") pcfg.replication = atoi(next().c_str());
     else if (a == "--stripe") pcfg.max_workers_per_copy = atoi(next().c_str());
-    else if (a == "--class") {
+    else if (a == "--range") {
+      const std::string r = next();
+      const auto colon = r.find(':');
+      if (colon == std::string::npos || colon == 0 || colon + 1 == r.size()) {
+        std::cerr << "--range wants OFF:LEN\n";
+        return 1;
+      }
+      ranged = true;
+      range_off = strtoull(r.substr(0, colon).c_str(), nullptr, 0);
+      range_len = strtoull(r.substr(colon + 1).c_str(), nullptr, 0);
+    } else if (a == "--class") {
       auto c = storage_class_from_string(next());
       if (c) pcfg.preferred_class = *c;
     } else if (a == "--help" || a == "-h") {
@@ -62,27 +76,40 @@ int main(int argc, char** argv) {
     return 1;
   };
 
+  // a file's bytes, or stdin's for "-"
+  auto slurp = [](const std::string& path, std::string& data) {
+    std::ostringstream ss;
+    if (path == "-") {
+      ss << std::cin.rdbuf();
+    } else {
+      std::ifstream in(path, std::ios::binary);
+      if (!in) {
+        std::cerr << "cannot open " << path << "\n";
+        return false;
+      }
+      ss << in.rdbuf();
+    }
+    data = ss.str();
+    return true;
+  };
+
   if (cmd == "put" && args.size() >= 3) {
     std::string data;
-    if (args[2] == "-") {
-      std::ostringstream ss;
-      ss << std::cin.rdbuf();
-      data = ss.str();
-    } else {
-      std::ifstream in(args[2], std::ios::binary);
-      if (!in) {
-        std::cerr << "cannot open " << args[2] << "\n";
-        return 1;
-      }
-      std::ostringstream ss;
-      ss << in.rdbuf();
-      data = ss.str();
-    }
+    if (!slurp(args[2], data)) return 1;
     auto r = client.put(args[1], data.data(), data.size(), pcfg);
     if (!r.ok()) return fail("put", r);
     std::cout << "stored " << args[1] << " (" << data.size() << " bytes)\n";
+  } else if (cmd == "patch" && args.size() >= 4) {
+    std::string data;
+    if (!slurp(args[3], data)) return 1;
+    const uint64_t off = strtoull(args[2].c_str(), nullptr, 0);
+    auto r = client.patch(args[1], off, data.data(), data.size());
+    if (!r.ok()) return fail("patch", r);
+    std::cout << "patched " << args[1] << " (" << data.size() << " bytes at "
+              << off << ")\n";
   } else if (cmd == "get" && args.size() >= 2) {
-    auto r = client.get(args[1]);
+    auto r = ranged ? client.get_range(args[1], range_off, range_len)
+                    : client.get(args[1]);
     if (!r.ok()) return fail("get", r);
     if (args.size() >= 3) {
       std::ofstream out(args[2], std::ios::binary);

@@ -549,6 +549,7 @@ PYBIND11_MODULE(_core, m) {
                                    first_tile);
   });
   gm.def("checksum_cpu_finalize", &gpu::checksum_cpu_finalize);
+  gm.def("checksum_cpu_unfinalize", &gpu::checksum_cpu_unfinalize);
   gm.def("checksum_cpu", [](py::buffer b) {
     py::buffer_info info = b.request();
     return gpu::checksum_cpu(info.ptr,
@@ -653,6 +654,77 @@ PYBIND11_MODULE(_core, m) {
     for (const auto& p : *plan) out.emplace_back(p.offset, p.nbytes, p.first_tile);
     return out;
   }, py::arg("obj_size"), py::arg("shard_lens"));
+  // in-place range patch: runs are (src, dst, nbytes, shard_tile, obj_tile,
+  // shard, obj) tuples; returns (shard digests, object digests)
+  using PatchTuples = std::vector<std::tuple<uint64_t, uint64_t, uint64_t,
+                                             uint64_t, uint64_t, uint32_t, uint32_t>>;
+  using U64s = std::vector<uint64_t>;
+  auto to_patch_segs = [](const PatchTuples& segs, const U64s& shard_lens,
+                          const U64s& shard_old, const U64s& obj_sizes,
+                          const U64s& obj_old) {
+    if (shard_lens.size() != shard_old.size() || obj_sizes.size() != obj_old.size())
+      throw BlackbirdError(ErrorCode::INVALID_ARGUMENT,
+                           "one old digest per shard and per object");
+    std::vector<gpu::PatchSeg> ss;
+    for (auto& [src, dst, n, shard_tile, obj_tile, shard, obj] : segs)
+      ss.push_back({reinterpret_cast<const void*>(src),
+                    reinterpret_cast<void*>(dst), n, shard_tile, obj_tile, shard,
+                    obj});
+    return ss;
+  };
+  gm.def("fused_patch", [to_patch_segs](const PatchTuples& segs,
+                                        const U64s& shard_lens, const U64s& shard_old,
+                                        const U64s& obj_sizes, const U64s& obj_old) {
+    auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+    // poisoned, as in fused_put
+    U64s shard_out(shard_lens.size(), ~0ull), obj_out(obj_sizes.size(), ~0ull);
+    py::gil_scoped_release rel;
+    unwrap_void(gpu::fused_patch(
+        ss.data(), static_cast<uint32_t>(ss.size()), shard_lens.data(),
+        shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
+        obj_sizes.data(), obj_old.data(), static_cast<uint32_t>(obj_sizes.size()),
+        shard_out.data(), obj_out.data(), nullptr));
+    return std::make_pair(shard_out, obj_out);
+  }, py::arg("segs"), py::arg("shard_lens"), py::arg("shard_old"),
+     py::arg("obj_sizes"), py::arg("obj_old"));
+  gm.def("patch_walk_depth", &gpu::patch_walk_depth);
+  // the argument check of fused_patch alone (no GPU): raises INVALID_ARGUMENT
+  gm.def("check_patch_segs", [to_patch_segs](const PatchTuples& segs,
+                                             const U64s& shard_lens,
+                                             const U64s& shard_old,
+                                             const U64s& obj_sizes,
+                                             const U64s& obj_old) {
+    auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+    unwrap_void(gpu::check_patch_segs(
+        ss.data(), static_cast<uint32_t>(ss.size()), shard_lens.data(),
+        shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
+        obj_sizes.data(), obj_old.data(),
+        static_cast<uint32_t>(obj_sizes.size())));
+  }, py::arg("segs"), py::arg("shard_lens"), py::arg("shard_old"),
+     py::arg("obj_sizes"), py::arg("obj_old"));
+  // a byte range of one copy → [(shard, shard_off, obj_off, nbytes)];
+  // plan_patch: None = not patchable in place; range_pieces: None = the range
+  // leaves the object or the lengths do not add up
+  using PieceTuples =
+      std::vector<std::tuple<uint32_t, uint64_t, uint64_t, uint64_t>>;
+  auto to_piece_tuples = [](const std::optional<std::vector<gpu::RangePiece>>& plan)
+      -> std::optional<PieceTuples> {
+    if (!plan) return std::nullopt;
+    PieceTuples out;
+    for (const auto& p : *plan)
+      out.emplace_back(p.shard, p.shard_off, p.obj_off, p.nbytes);
+    return out;
+  };
+  gm.def("plan_patch", [to_piece_tuples](uint64_t obj_size, const U64s& shard_lens,
+                                         uint64_t offset, uint64_t length) {
+    return to_piece_tuples(gpu::plan_patch(obj_size, shard_lens, offset, length));
+  }, py::arg("obj_size"), py::arg("shard_lens"), py::arg("offset"),
+     py::arg("length"));
+  gm.def("range_pieces", [to_piece_tuples](uint64_t obj_size, const U64s& shard_lens,
+                                           uint64_t offset, uint64_t length) {
+    return to_piece_tuples(gpu::range_pieces(obj_size, shard_lens, offset, length));
+  }, py::arg("obj_size"), py::arg("shard_lens"), py::arg("offset"),
+     py::arg("length"));
   // one FusedPutPlan, replayed `steps` times: one digest list per step
   gm.def("fused_put_plan",
          [to_put_descs](const DescTuples& descs, int steps, int device) {

@@ -138,6 +138,16 @@ void bind_store(py::module_& m) {
       .def("remove_object", [](KeystoneService& k, const std::string& key) {
         unwrap_void(k.remove_object(key));
       })
+      // in-place range patches: [(status, GetWorkersResponse)] per key — the
+      // answer is meaningful where the status is 0 — and [status] per key
+      .def("batch_patch_start", [](KeystoneService& k,
+                                   const std::vector<std::string>& keys) {
+        std::vector<std::pair<int32_t, GetWorkersResponse>> out;
+        for (auto& it : k.batch_patch_start(keys).items)
+          out.emplace_back(it.status, std::move(it.info));
+        return out;
+      })
+      .def("batch_patch_abort", &KeystoneService::batch_patch_abort)
       .def("remove_all_objects", &KeystoneService::remove_all_objects)
       .def("get_workers_info", &KeystoneService::get_workers_info)
       .def("get_memory_pools", &KeystoneService::get_memory_pools)
@@ -348,6 +358,22 @@ void bind_store(py::module_& m) {
         }
         return py::bytes(out);
       })
+      .def("get_range", [](Client& c, const std::string& key, uint64_t offset,
+                           uint64_t length) {
+        std::string out;
+        {
+          py::gil_scoped_release rel;
+          out = unwrap(c.get_range(key, offset, length));
+        }
+        return py::bytes(out);
+      }, py::arg("key"), py::arg("offset"), py::arg("length"))
+      .def("patch", [](Client& c, const std::string& key, uint64_t offset,
+                       py::buffer buf) {
+        py::buffer_info info = buf.request();
+        py::gil_scoped_release rel;
+        unwrap_void(c.patch(key, offset, info.ptr,
+                            static_cast<uint64_t>(info.size * info.itemsize)));
+      }, py::arg("key"), py::arg("offset"), py::arg("data"))
       .def("exists", [](Client& c, const std::string& key) {
         return unwrap(c.exists(key));
       }, py::call_guard<py::gil_scoped_release>())
@@ -540,6 +566,41 @@ void bind_store(py::module_& m) {
              py::gil_scoped_release rel;
              return unwrap(g.batch_get_device(b.items, verify, &b.session));
            }, py::arg("batch"), py::arg("verify") = false)
+      // ranged calls: items are (key, offset, dev_ptr, length)
+      .def("batch_get_device_range",
+           [](GpuClient& g, const std::vector<std::tuple<std::string, uint64_t,
+                                                         uint64_t, uint64_t>>& items) {
+             std::vector<GpuClient::DevRangeGet> its;
+             for (auto& [k, off, p, n] : items)
+               its.push_back({k, off, reinterpret_cast<void*>(p), n});
+             py::gil_scoped_release rel;
+             return unwrap(g.batch_get_device_range(its));
+           }, py::arg("items"))
+      .def("get_device_range", [](GpuClient& g, const std::string& key,
+                                  uint64_t offset, uint64_t ptr, uint64_t length) {
+        unwrap_void(g.get_device_range(key, offset, reinterpret_cast<void*>(ptr),
+                                       length));
+      }, py::arg("key"), py::arg("offset"), py::arg("dev_ptr"), py::arg("length"),
+         py::call_guard<py::gil_scoped_release>())
+      .def("batch_patch_device",
+           [](GpuClient& g, const std::vector<std::tuple<std::string, uint64_t,
+                                                         uint64_t, uint64_t>>& items) {
+             std::vector<GpuClient::DevRangePatch> its;
+             for (auto& [k, off, p, n] : items)
+               its.push_back({k, off, reinterpret_cast<const void*>(p), n});
+             py::gil_scoped_release rel;
+             return unwrap(g.batch_patch_device(its));
+           }, py::arg("items"))
+      .def("patch_device", [](GpuClient& g, const std::string& key,
+                              uint64_t offset, uint64_t ptr, uint64_t length) {
+        unwrap_void(g.patch_device(key, offset, reinterpret_cast<const void*>(ptr),
+                                   length));
+      }, py::arg("key"), py::arg("offset"), py::arg("dev_ptr"), py::arg("length"),
+         py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("patched_fused_items",
+                             &GpuClient::patched_fused_items)
+      .def_property_readonly("patched_rewrite_items",
+                             &GpuClient::patched_rewrite_items)
       .def_property_readonly("session_put_steps", &GpuClient::session_put_steps)
       .def_property_readonly("striped_fused_items",
                              &GpuClient::striped_fused_items)

@@ -424,6 +424,199 @@ Result<uint64_t> Client::get_into(const ObjectKey& key, void* dst,
   return meta->size;
 }
 
+// ---------------------------------------------------------- ranged access
+
+namespace {
+// Whether the tier serves this sub-range as such. The block tiers do IO at
+// 4 KiB granularity (an unaligned write there is a read-modify-write of its
+// edge blocks), so a piece that is not made of whole blocks goes through the
+// whole shard or the whole object instead.
+bool sub_shard_ok(const ShardPlacement& s, const gpu::RangePiece& p) {
+  switch (s.storage_class) {
+    case StorageClass::NVME:
+    case StorageClass::SSD:
+    case StorageClass::HDD:
+      return (s.offset + p.shard_off) % 4096 == 0 &&
+             (p.nbytes % 4096 == 0 || p.shard_off + p.nbytes == s.length);
+    default:
+      return true;
+  }
+}
+}  // namespace
+
+Result<std::string> Client::get_range(const ObjectKey& key, uint64_t offset,
+                                      uint64_t length) {
+  auto meta = meta_call<KeyMsg, GetWorkersResponse>(M::GET_WORKERS, KeyMsg{key},
+                                                     opts_.rpc_timeout_ms);
+  if (!meta.ok()) return meta.error();
+  if (!range_inside(offset, length, meta->size))
+    return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + key};
+  std::string out;
+  out.resize(length);
+  Error last{ErrorCode::NO_PLACEMENT, "no copies"};
+  for (const auto& copy : meta->copies) {
+    auto pieces = gpu::range_pieces(meta->size, shard_lens_of(copy), offset, length);
+    if (!pieces) continue;  // the copy does not cover the object
+    bool ok = true;
+    for (const auto& p : *pieces) {
+      const ShardPlacement& s = copy.shards[p.shard];
+      char* dst = out.data() + (p.obj_off - offset);
+      Result<void> r;
+      if (sub_shard_ok(s, p)) {
+        r = read_shard(sub_shard(s, p.shard_off, p.nbytes), dst);
+      } else {
+        std::string whole(s.length, '\0');
+        r = read_shard(s, whole.data());
+        if (r.ok()) std::memcpy(dst, whole.data() + p.shard_off, p.nbytes);
+      }
+      if (!r.ok()) {
+        ok = false;
+        last = r.error();
+        break;
+      }
+    }
+    if (ok) return out;
+  }
+  return last;
+}
+
+Result<BatchGetWorkersResponse> Client::patch_start(
+    const std::vector<ObjectKey>& keys) {
+  auto resp = meta_call<KeysMsg, BatchGetWorkersResponse>(
+      M::BATCH_PATCH_START, KeysMsg{keys}, opts_.rpc_timeout_ms);
+  if (resp.ok() && resp->items.size() != keys.size())
+    return Error{ErrorCode::PROTOCOL_ERROR, "patch start: item count"};
+  return resp;
+}
+
+void Client::patch_abort(const std::vector<ObjectKey>& keys) {
+  if (keys.empty()) return;
+  meta_call_raw(M::BATCH_PATCH_ABORT, serde::to_bytes(KeysMsg{keys}),
+                opts_.rpc_timeout_ms);
+}
+
+Result<void> Client::patch(const ObjectKey& key, uint64_t offset,
+                           const void* data, uint64_t size) {
+  const uint8_t* new_bytes = static_cast<const uint8_t*>(data);
+  // get, overlay, put back: right on every tier and placement
+  auto rewrite = [&](const GetWorkersResponse& info) -> Result<void> {
+    std::string whole(info.size, '\0');
+    BB_RETURN_IF_ERROR(read_copy(info.copies, whole.data(), info.size));
+    if (info.checksum != 0 &&
+        gpu::checksum_cpu(whole.data(), whole.size()) != info.checksum)
+      return Error{ErrorCode::CHECKSUM_MISMATCH, key};
+    std::memcpy(whole.data() + offset, new_bytes, size);
+    PlacementConfig cfg;
+    cfg.replace = true;
+    cfg.replication = static_cast<uint32_t>(info.copies.size());
+    for (const auto& c : info.copies)
+      cfg.max_workers_per_copy = std::max<uint32_t>(
+          cfg.max_workers_per_copy, static_cast<uint32_t>(c.shards.size()));
+    if (!info.copies.empty() && !info.copies[0].shards.empty())
+      cfg.preferred_class = info.copies[0].shards[0].storage_class;
+    return put(key, whole.data(), whole.size(), cfg);
+  };
+  auto in_range = [&](uint64_t obj_size) {
+    return range_inside(offset, size, obj_size);
+  };
+
+  auto started = patch_start({key});
+  if (!started.ok()) return started.error();
+  const auto& item = started->items[0];
+  if (item.status == static_cast<int32_t>(ErrorCode::INVALID_STATE)) {
+    // no recorded checksum: nothing to move, and no state was changed
+    auto meta = meta_call<KeyMsg, GetWorkersResponse>(M::GET_WORKERS, KeyMsg{key},
+                                                       opts_.rpc_timeout_ms);
+    if (!meta.ok()) return meta.error();
+    if (!in_range(meta->size))
+      return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + key};
+    return rewrite(meta.value());
+  }
+  if (item.status != 0)
+    return Error{static_cast<ErrorCode>(item.status), key};
+  const GetWorkersResponse& info = item.info;
+  if (!in_range(info.size)) {
+    patch_abort({key});
+    return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + key};
+  }
+
+  // every copy's pieces, or the rewrite route
+  std::vector<std::vector<gpu::RangePiece>> plans;
+  bool in_place = !info.copies.empty();
+  for (const auto& copy : info.copies) {
+    auto pieces = gpu::plan_patch(info.size, shard_lens_of(copy), offset, size);
+    if (!pieces) {
+      in_place = false;
+      break;
+    }
+    for (const auto& s : copy.shards)
+      if (s.digest == 0) in_place = false;
+    for (const auto& p : *pieces)
+      if (!sub_shard_ok(copy.shards[p.shard], p)) in_place = false;
+    plans.push_back(std::move(*pieces));
+  }
+  if (!in_place) {
+    patch_abort({key});
+    return rewrite(info);
+  }
+
+  // old bytes first — nothing is written until every copy's new digests are
+  // known and agree
+  using digest::kTileBytes;
+  PutCompleteRequest done_req{key, 0, {}};
+  std::string old(size, '\0');
+  for (size_t c = 0; c < info.copies.size(); ++c) {
+    const auto& copy = info.copies[c];
+    uint64_t h = gpu::checksum_cpu_unfinalize(info.checksum, info.size);
+    std::vector<uint64_t> sums;
+    for (const auto& s : copy.shards)
+      sums.push_back(gpu::checksum_cpu_unfinalize(s.digest, s.length));
+    for (const auto& p : plans[c]) {
+      const uint64_t at = p.obj_off - offset;
+      auto r = read_shard(sub_shard(copy.shards[p.shard], p.shard_off, p.nbytes),
+                          old.data() + at);
+      if (!r.ok()) {
+        patch_abort({key});
+        return r.error();
+      }
+      const uint64_t ot = p.obj_off / kTileBytes, st = p.shard_off / kTileBytes;
+      h += gpu::checksum_cpu_tiles(new_bytes + at, p.nbytes, ot) -
+           gpu::checksum_cpu_tiles(old.data() + at, p.nbytes, ot);
+      sums[p.shard] += gpu::checksum_cpu_tiles(new_bytes + at, p.nbytes, st) -
+                       gpu::checksum_cpu_tiles(old.data() + at, p.nbytes, st);
+    }
+    const uint64_t checksum = gpu::checksum_cpu_finalize(h, info.size);
+    if (c > 0 && checksum != done_req.checksum) {
+      patch_abort({key});
+      return Error{ErrorCode::CHECKSUM_MISMATCH, "replicas of " + key + " diverged"};
+    }
+    done_req.checksum = checksum;
+    for (size_t s = 0; s < sums.size(); ++s)
+      sums[s] = gpu::checksum_cpu_finalize(sums[s], copy.shards[s].length);
+    done_req.shard_digests.push_back(std::move(sums));
+  }
+  for (size_t c = 0; c < info.copies.size(); ++c)
+    for (const auto& p : plans[c]) {
+      auto r = write_shard(
+          sub_shard(info.copies[c].shards[p.shard], p.shard_off, p.nbytes),
+          new_bytes + (p.obj_off - offset));
+      if (!r.ok()) {  // torn
+        cancel_puts({key});
+        return r.error();
+      }
+    }
+  auto done = meta_call_raw(M::BATCH_PUT_COMPLETE,
+                            serde::to_bytes(PutCompleteListMsg{{done_req}}),
+                            opts_.rpc_timeout_ms);
+  if (!done.ok()) return done.error();
+  StatusListMsg st;
+  if (!serde::from_bytes(done.value(), st) || st.statuses.size() != 1)
+    return Error{ErrorCode::PROTOCOL_ERROR, "patch commit answer"};
+  if (st.statuses[0] != 0)
+    return Error{static_cast<ErrorCode>(st.statuses[0]), key};
+  return {};
+}
+
 Result<bool> Client::exists(const ObjectKey& key) {
   auto r = meta_call<KeyMsg, BoolMsg>(M::OBJECT_EXISTS, KeyMsg{key},
                                        opts_.rpc_timeout_ms);

@@ -636,6 +636,280 @@ Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
   return last;
 }
 
+// ----------------------------------------------------------- ranged access
+
+Result<std::vector<int32_t>> GpuClient::batch_get_device_range(
+    const std::vector<DevRangeGet>& items) {
+  std::vector<int32_t> statuses(items.size(), 0);
+  if (items.empty()) return statuses;
+  BB_RETURN_IF_ERROR(init());
+  BB_HIP(hipSetDevice(device_));
+  KeysMsg req;
+  for (const auto& it : items) req.keys.push_back(it.key);
+  auto resp = c_.meta_call<KeysMsg, BatchGetWorkersResponse>(
+      M::BATCH_GET_WORKERS, req, c_.opts_.rpc_timeout_ms);
+  if (!resp.ok()) return resp.error();
+  if (resp->items.size() != items.size())
+    return Error{ErrorCode::PROTOCOL_ERROR, "batch_get_workers: item count"};
+
+  std::vector<gpu::CopyDesc> descs;  // the one batched_copy launch
+  for (size_t i = 0; i < items.size(); ++i) {
+    const auto& it = items[i];
+    const auto& info = resp->items[i].info;
+    if (resp->items[i].status != 0) {
+      statuses[i] = resp->items[i].status;
+      continue;
+    }
+    if (!range_inside(it.offset, it.length, info.size)) {
+      statuses[i] = static_cast<int32_t>(ErrorCode::INVALID_ARGUMENT);
+      continue;
+    }
+    statuses[i] = static_cast<int32_t>(ErrorCode::NO_PLACEMENT);
+    for (const auto& copy : info.copies) {
+      auto pieces =
+          gpu::range_pieces(info.size, shard_lens_of(copy), it.offset, it.length);
+      if (!pieces) continue;  // the copy does not cover the object
+      const size_t mark = descs.size();
+      Result<void> r{};
+      for (const auto& p : *pieces) {
+        const ShardPlacement& s = copy.shards[p.shard];
+        uint8_t* user = static_cast<uint8_t*>(it.ptr) + (p.obj_off - it.offset);
+        if (uint8_t* pool = resolve_device_ptr(s)) {
+          descs.push_back({pool + p.shard_off, user, p.nbytes});
+          continue;
+        }
+        if (s.length <= staging_size_) {
+          // the whole shard into staging (what every tier serves), then the
+          // slice
+          std::lock_guard<std::mutex> g(staging_mu_);
+          r = c_.read_shard(s, staging_);
+          if (r.ok())
+            r = gpu::copy_sync(user, static_cast<uint8_t*>(staging_) + p.shard_off,
+                               p.nbytes, hipMemcpyHostToDevice);
+        } else {
+          r = staged_read(sub_shard(s, p.shard_off, p.nbytes), user);
+        }
+        if (!r.ok()) break;
+      }
+      if (r.ok()) {
+        statuses[i] = 0;
+        break;
+      }
+      descs.resize(mark);  // next replica
+      statuses[i] = static_cast<int32_t>(r.code());
+    }
+  }
+  if (!descs.empty()) {
+    BB_RETURN_IF_ERROR(gpu::batched_copy(
+        descs.data(), static_cast<uint32_t>(descs.size()), streams_[0]));
+    BB_HIP(hipStreamSynchronize(streams_[0]));
+  }
+  return statuses;
+}
+
+Result<void> GpuClient::get_device_range(const ObjectKey& key, uint64_t offset,
+                                         void* dev_ptr, uint64_t length) {
+  auto r = batch_get_device_range({DevRangeGet{key, offset, dev_ptr, length}});
+  if (!r.ok()) return r.error();
+  if (r.value()[0] != 0)
+    return Error{static_cast<ErrorCode>(r.value()[0]), key};
+  return {};
+}
+
+Result<void> GpuClient::patch_by_rewrite(const DevRangePatch& item,
+                                         const GetWorkersResponse& info) {
+  if (!range_inside(item.offset, item.length, info.size))
+    return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + item.key};
+  void* tmp = nullptr;
+  BB_HIP(hipMalloc(&tmp, std::max<uint64_t>(info.size, 16)));
+  auto run = [&]() -> Result<void> {
+    auto got = get_device(item.key, tmp, info.size, /*verify=*/true);
+    if (!got.ok()) return got.error();
+    BB_RETURN_IF_ERROR(gpu::copy_sync(static_cast<uint8_t*>(tmp) + item.offset,
+                                      item.ptr, item.length,
+                                      hipMemcpyDeviceToDevice));
+    PlacementConfig cfg;
+    cfg.replace = true;
+    cfg.replication = static_cast<uint32_t>(info.copies.size());
+    for (const auto& c : info.copies)
+      cfg.max_workers_per_copy = std::max<uint32_t>(
+          cfg.max_workers_per_copy, static_cast<uint32_t>(c.shards.size()));
+    if (!info.copies.empty() && !info.copies[0].shards.empty())
+      cfg.preferred_class = info.copies[0].shards[0].storage_class;
+    return put_device(item.key, tmp, info.size, cfg);
+  };
+  auto r = run();
+  (void)hipFree(tmp);
+  return r;
+}
+
+Result<std::vector<int32_t>> GpuClient::batch_patch_device(
+    const std::vector<DevRangePatch>& items) {
+  std::vector<int32_t> statuses(items.size(), 0);
+  if (items.empty()) return statuses;
+  BB_RETURN_IF_ERROR(init());
+  BB_HIP(hipSetDevice(device_));
+  std::vector<ObjectKey> keys;
+  for (const auto& it : items) keys.push_back(it.key);
+  auto started = c_.patch_start(keys);
+  if (!started.ok()) return started.error();
+  // the patched keys leave the cache whatever becomes of them; this also
+  // unbinds every session
+  {
+    PlacementCache::KeyList list;
+    for (const auto& k : keys) list.push_back(&k);
+    cache_.erase(list);
+  }
+
+  // the one fused_patch launch: every copy of an item is a kernel object of
+  // its own, so diverged replicas show as different digests
+  struct Fused {
+    uint32_t item;
+    uint32_t first_obj, ncopies;
+    uint32_t first_shard;  // shards of copy 0, copy 1, … back to back
+  };
+  std::vector<gpu::PatchSeg> segs;
+  std::vector<uint64_t> shard_lens, shard_old, obj_sizes, obj_old;
+  std::vector<Fused> fused;
+  std::vector<uint32_t> rewrite;  // item indices
+  std::vector<GetWorkersResponse> rewrite_info(items.size());
+  std::vector<ObjectKey> aborts;
+
+  for (size_t i = 0; i < items.size(); ++i) {
+    const auto& it = items[i];
+    auto& got = started->items[i];
+    if (got.status == static_cast<int32_t>(ErrorCode::INVALID_STATE)) {
+      // no recorded checksum, no state changed: what is there to rewrite?
+      auto meta = c_.meta_call<KeyMsg, GetWorkersResponse>(
+          M::GET_WORKERS, KeyMsg{it.key}, c_.opts_.rpc_timeout_ms);
+      if (!meta.ok()) {
+        statuses[i] = static_cast<int32_t>(meta.code());
+        continue;
+      }
+      rewrite_info[i] = std::move(meta.value());
+      rewrite.push_back(static_cast<uint32_t>(i));
+      continue;
+    }
+    if (got.status != 0) {
+      statuses[i] = got.status;
+      continue;
+    }
+    const GetWorkersResponse& info = got.info;
+    if (!range_inside(it.offset, it.length, info.size)) {
+      statuses[i] = static_cast<int32_t>(ErrorCode::INVALID_ARGUMENT);
+      aborts.push_back(it.key);
+      continue;
+    }
+    const size_t seg_mark = segs.size(), shard_mark = shard_lens.size(),
+                 obj_mark = obj_sizes.size();
+    bool in_place = !info.copies.empty();
+    for (size_t c = 0; in_place && c < info.copies.size(); ++c) {
+      const auto& copy = info.copies[c];
+      auto pieces =
+          gpu::plan_patch(info.size, shard_lens_of(copy), it.offset, it.length);
+      if (!pieces) {
+        in_place = false;
+        break;
+      }
+      const uint32_t shard0 = static_cast<uint32_t>(shard_lens.size());
+      const uint32_t obj = static_cast<uint32_t>(obj_sizes.size());
+      for (const auto& s : copy.shards) {
+        if (s.digest == 0) in_place = false;
+        shard_lens.push_back(s.length);
+        shard_old.push_back(s.digest);
+      }
+      obj_sizes.push_back(info.size);
+      obj_old.push_back(info.checksum);
+      for (const auto& p : *pieces) {
+        uint8_t* pool = resolve_device_ptr(copy.shards[p.shard]);
+        const uint8_t* src =
+            static_cast<const uint8_t*>(it.ptr) + (p.obj_off - it.offset);
+        if (!pool || !aligned16(pool + p.shard_off, src)) {
+          in_place = false;
+          break;
+        }
+        segs.push_back({src, pool + p.shard_off, p.nbytes,
+                        p.shard_off / digest::kTileBytes,
+                        p.obj_off / digest::kTileBytes, shard0 + p.shard, obj});
+      }
+    }
+    if (!in_place) {
+      segs.resize(seg_mark);
+      shard_lens.resize(shard_mark);
+      shard_old.resize(shard_mark);
+      obj_sizes.resize(obj_mark);
+      obj_old.resize(obj_mark);
+      aborts.push_back(it.key);
+      rewrite_info[i] = info;
+      rewrite.push_back(static_cast<uint32_t>(i));
+      continue;
+    }
+    fused.push_back({static_cast<uint32_t>(i), static_cast<uint32_t>(obj_mark),
+                     static_cast<uint32_t>(info.copies.size()),
+                     static_cast<uint32_t>(shard_mark)});
+  }
+  c_.patch_abort(aborts);
+
+  if (!fused.empty()) {
+    std::vector<uint64_t> shard_new(shard_lens.size()), obj_new(obj_sizes.size());
+    auto launched = gpu::fused_patch(
+        segs.data(), static_cast<uint32_t>(segs.size()), shard_lens.data(),
+        shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
+        obj_sizes.data(), obj_old.data(), static_cast<uint32_t>(obj_sizes.size()),
+        shard_new.data(), obj_new.data(), streams_[2]);
+    std::vector<ObjectKey> cancels;
+    std::vector<PutCompleteRequest> reqs;
+    std::vector<uint32_t> order;
+    for (const auto& f : fused) {
+      const ObjectKey& key = items[f.item].key;
+      if (!launched.ok()) {  // torn
+        statuses[f.item] = static_cast<int32_t>(launched.code());
+        cancels.push_back(key);
+        continue;
+      }
+      bool agree = true;
+      for (uint32_t c = 1; c < f.ncopies; ++c)
+        if (obj_new[f.first_obj + c] != obj_new[f.first_obj]) agree = false;
+      if (!agree) {
+        statuses[f.item] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
+        cancels.push_back(key);
+        continue;
+      }
+      PutCompleteRequest pc{key, obj_new[f.first_obj], {}};
+      uint32_t at = f.first_shard;
+      for (const auto& copy : started->items[f.item].info.copies) {
+        pc.shard_digests.emplace_back(shard_new.begin() + at,
+                                      shard_new.begin() + at + copy.shards.size());
+        at += static_cast<uint32_t>(copy.shards.size());
+      }
+      reqs.push_back(std::move(pc));
+      order.push_back(f.item);
+    }
+    c_.cancel_puts(cancels);
+    if (!reqs.empty()) {
+      BB_RETURN_IF_ERROR(c_.complete_by_keys(reqs, order, &statuses));
+      for (uint32_t i : order)
+        if (statuses[i] == 0) ++patched_fused_items_;
+    }
+  }
+
+  for (uint32_t i : rewrite) {
+    auto r = patch_by_rewrite(items[i], rewrite_info[i]);
+    statuses[i] = static_cast<int32_t>(r.code());
+    if (r.ok()) ++patched_rewrite_items_;
+  }
+  return statuses;
+}
+
+Result<void> GpuClient::patch_device(const ObjectKey& key, uint64_t offset,
+                                     const void* dev_ptr, uint64_t length) {
+  auto r = batch_patch_device({DevRangePatch{key, offset, dev_ptr, length}});
+  if (!r.ok()) return r.error();
+  if (r.value()[0] != 0)
+    return Error{static_cast<ErrorCode>(r.value()[0]), key};
+  return {};
+}
+
 
 // ------------------------ compact v2 batch protocol ------------------------
 // Pool-table responses with fixed-width placements: the client resolves each

@@ -143,6 +143,10 @@ uint64_t checksum_cpu_finalize(uint64_t h, uint64_t object_nbytes) {
   return finalize(h, object_nbytes);
 }
 
+uint64_t checksum_cpu_unfinalize(uint64_t digest, uint64_t object_nbytes) {
+  return unfinalize(digest, object_nbytes);
+}
+
 uint64_t checksum_cpu(const void* ptr, uint64_t nbytes) {
   const uint8_t* p = static_cast<const uint8_t*>(ptr);
   const uint64_t ntiles = (nbytes + kTileBytes - 1) / kTileBytes;

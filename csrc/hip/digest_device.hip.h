@@ -430,4 +430,177 @@ __device__ __forceinline__ void digest_walk(
   if constexpr (kStripe) flush_object();
 }
 
+// Tiles per load stream (old and new) that the patch walk keeps in flight:
+// 2 × 2 loads, as many as the copying walk's kWalkDepth, on twice the
+// fragment registers per tile.
+constexpr int kPatchDepth = 2;
+
+// The sibling walk of the in-place range patch (patch.hip). One run = one
+// PatchSeg: new bytes at src that replace the old ones at dst, from a tile
+// boundary of the run's shard and of its object. The ranges, the boundary
+// bookkeeping and the tile helpers are digest_walk's; what differs is that
+// every tile is loaded twice — old from dst, new from src — both fragments
+// go through the MFMA and the group fold, and the sums take the DIFFERENCE
+// mix_slot(f_new, slot) − mix_slot(f_old, slot) (u64 wraparound):
+// shard_acc[run.shard] with slots counted from the shard's start,
+// obj_acc[run.obj] with slots counted from the object's start. The host
+// seeds both with unfinalize(old digest); nothing is cleared here. A run at
+// the same tile of both (a single-shard object, or the first shard) runs one
+// pair of mixes and adds it to both.
+//
+// Ordering: a tile's new bytes go to dst only after the load of its old
+// bytes has returned. Per tile the old load is issued BEFORE the new load
+// (the scheduling barrier between them keeps it so), vector loads return in
+// order, and the store's data is the new fragment — so the wait the store
+// needs covers the old load as well. The tail tile's byte accesses wait for
+// everything explicitly. Nothing leans on the memory system's order between
+// a load and a younger store to one address.
+//
+// Both loads are nontemporal: the old tile is overwritten at once and the
+// new one is not read again (unmeasured against plain loads).
+template <int kDepth>
+__device__ __forceinline__ void patch_walk(
+    const PatchSeg* __restrict__ segs, const uint64_t* __restrict__ tile_prefix,
+    uint32_t nseg, uint64_t total_tiles,
+    unsigned long long* __restrict__ shard_acc,
+    unsigned long long* __restrict__ obj_acc) {
+  static_assert(kDepth >= 1);
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = wave_uniform(threadIdx.x >> 6);
+  const uint64_t gwave =
+      static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
+  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
+  const uint64_t per = (total_tiles + nwaves - 1) / nwaves;
+  const uint64_t begin = gwave * per;
+  const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
+  if (begin >= total_tiles) return;
+
+  const i32x4 b_frag = load_b_frag(lane);
+  const WReg wr = load_w_reg(lane);
+  const uint32_t lane_off = lane_tile_offset(lane);
+
+  uint32_t si = wave_uniform(find_seg(tile_prefix, nseg, begin));
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t nbytes, cur_full, shard_slot, obj_slot;
+  uint32_t shard, obj;
+  uint64_t base_tile, next_boundary;
+  auto enter_run = [&] {
+    const PatchSeg d = segs[si];
+    src = wave_uniform(static_cast<const uint8_t*>(d.src));
+    dst = wave_uniform(static_cast<uint8_t*>(d.dst));
+    nbytes = wave_uniform(d.nbytes);
+    cur_full = nbytes / kTileBytes;
+    shard_slot = wave_uniform(d.shard_tile) * 64;
+    obj_slot = wave_uniform(d.obj_tile) * 64;
+    shard = wave_uniform(d.shard);
+    obj = wave_uniform(d.obj);
+    next_boundary =
+        (si + 1 < nseg) ? wave_uniform(tile_prefix[si + 1]) : ~0ull;
+  };
+  enter_run();
+  base_tile = wave_uniform(tile_prefix[si]);
+
+  uint64_t hs = 0, ho = 0;  // the shard-slot and object-slot differences
+  // leaving a run: its shares of the two accumulators
+  auto flush = [&] {
+    hs = wave_sum_u64(hs);
+    if (shard_slot != obj_slot) ho = wave_sum_u64(ho);
+    else ho = hs;
+    if (lane == 0 && hs != 0) atomicAdd(&shard_acc[shard], hs);
+    if (lane == 0 && ho != 0) atomicAdd(&obj_acc[obj], ho);
+    hs = ho = 0;
+  };
+  // tile t of the current run, old and new projected
+  auto fold = [&](const i32x16& acc_old, const i32x16& acc_new, uint64_t t) {
+    const uint64_t f_old = fold_group(acc_old, wr);
+    const uint64_t f_new = fold_group(acc_new, wr);
+    const uint64_t slot = t * 64 + lane;
+    hs += mix_slot(f_new, shard_slot + slot) - mix_slot(f_old, shard_slot + slot);
+    if (shard_slot != obj_slot)
+      ho += mix_slot(f_new, obj_slot + slot) - mix_slot(f_old, obj_slot + slot);
+  };
+  struct Pair {
+    i32x4 o, n;
+  };
+  // old first, then new: see "Ordering" above
+  auto load_pair = [&](uint64_t tile) {
+    Pair p;
+    p.o = load_a_frag<true>(dst + tile * kTileBytes, lane_off);
+    __builtin_amdgcn_sched_barrier(0);
+    p.n = load_a_frag<true>(src + tile * kTileBytes, lane_off);
+    __builtin_amdgcn_sched_barrier(0);
+    return p;
+  };
+  // n >= 1 full tiles of the current run, from its tile t0
+  auto full_run = [&](uint64_t t0, uint32_t n) {
+    auto plain = [&](uint32_t i, uint32_t stop) {
+      for (; i < stop; ++i) {
+        const Pair p = load_pair(t0 + i);
+        store_a_frag(dst + (t0 + i) * kTileBytes, lane_off, p.n);
+        fold(project_tile(p.o, b_frag), project_tile(p.n, b_frag), t0 + i);
+      }
+    };
+    if (n < 2u * kDepth) {
+      plain(0, n);
+      return;
+    }
+    // buf[k] holds tile i+k, then tile i+k+kDepth, as in digest_walk
+    Pair buf[kDepth];
+    auto step = [&](uint32_t k, uint32_t i, bool refill) {
+      store_a_frag(dst + (t0 + i + k) * kTileBytes, lane_off, buf[k].n);
+      const i32x16 acc_old = project_tile(buf[k].o, b_frag);
+      const i32x16 acc_new = project_tile(buf[k].n, b_frag);
+      __builtin_amdgcn_sched_barrier(0);
+      if (refill) buf[k] = load_pair(t0 + i + k + kDepth);
+      __builtin_amdgcn_sched_barrier(0);
+      fold(acc_old, acc_new, t0 + i + k);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) buf[k] = load_pair(t0 + k);
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+    for (i = kDepth; i + 2u * kDepth <= n; i += kDepth) {
+#pragma unroll
+      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, false);
+    plain(i + kDepth, n);
+  };
+
+  uint64_t gt = begin;
+  while (gt < end) {
+    while (gt >= next_boundary) {
+      flush();
+      ++si;
+      base_tile = next_boundary;
+      enter_run();
+    }
+    const uint64_t t = gt - base_tile;
+    const uint64_t stop =
+        (end < next_boundary ? end : next_boundary) - base_tile;
+    const uint64_t full_stop = stop < cur_full ? stop : cur_full;
+    if (t < full_stop) {
+      const uint64_t left = full_stop - t;
+      const uint32_t n = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
+      full_run(t, n);
+      gt += n;
+    } else {
+      // tail tile: byte-guarded loads of both, zero-padded; every load has
+      // returned before the first byte is stored
+      const uint64_t toff = t * kTileBytes;
+      const i32x4 a_old = load_a_frag_guarded(dst, toff, nbytes, lane_off);
+      const i32x4 a_new = load_a_frag_guarded(src, toff, nbytes, lane_off);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      store_a_frag_guarded(dst, toff, nbytes, lane_off, a_new);
+      fold(project_tile(a_old, b_frag), project_tile(a_new, b_frag), t);
+      ++gt;
+    }
+  }
+  flush();
+}
+
 }  // namespace blackbird::gpu::dev

@@ -1,5 +1,6 @@
 // Pieces the host Client and GpuClient share in their batch paths: the item
-// fan-out and the resolved pool table of a v2 response. Host-only (no HIP).
+// fan-out, the resolved pool table of a v2 response and the small steps of
+// the ranged calls. Host-only (no HIP).
 #pragma once
 
 #include <cstdint>
@@ -35,6 +36,30 @@ std::vector<PoolRef> resolve_pool_table(const std::vector<PoolId>& ids,
     pools[i].base = base_of(ids[i], &pools[i].access);
   }
   return pools;
+}
+
+// ---- ranged access ----
+// a copy's shard lengths, for the planners of gpu/patch_plan.h
+inline std::vector<uint64_t> shard_lens_of(const CopyPlacement& copy) {
+  std::vector<uint64_t> lens;
+  lens.reserve(copy.shards.size());
+  for (const auto& s : copy.shards) lens.push_back(s.length);
+  return lens;
+}
+
+// [offset, offset+length) lies inside an object of `size` bytes
+inline bool range_inside(uint64_t offset, uint64_t length, uint64_t size) {
+  return offset <= size && length <= size - offset;
+}
+
+// [shard_off, shard_off+n) of `s` as a placement of its own, for the shard
+// movers
+inline ShardPlacement sub_shard(const ShardPlacement& s, uint64_t shard_off,
+                                uint64_t n) {
+  ShardPlacement sub = s;
+  sub.offset = s.offset + shard_off;
+  sub.length = n;
+  return sub;
 }
 
 }  // namespace blackbird

@@ -61,6 +61,31 @@ class Client {
                    const PlacementConfig& cfg = {});
   Result<std::string> get(const ObjectKey& key);
   Result<uint64_t> get_into(const ObjectKey& key, void* dst, uint64_t capacity);
+  // ---- ranged access ----
+  // [offset, offset+length) of the object: the intersecting sub-ranges of the
+  // first copy that reads completely, with replica failover as in get. Any
+  // offset and length inside the object; a range that leaves it is
+  // INVALID_ARGUMENT. UNVERIFIED, whatever verify_checksum_on_get says: the
+  // recorded digests cover whole shards and whole objects, never a range.
+  Result<std::string> get_range(const ObjectKey& key, uint64_t offset,
+                                uint64_t length);
+  // Overwrites [offset, offset+size) of a committed object in place, on
+  // every copy, and moves the recorded object checksum and shard digests by
+  // the patched tiles' terms alone (gpu/patch_plan.h): BATCH_PATCH_START,
+  // read the old range, write the new one, BATCH_PUT_COMPLETE. Bytes outside
+  // the range are neither read nor re-hashed, so corruption there stays
+  // detectable. A range that is not made of whole 1 KiB tiles (but for one
+  // that ends at the object's end), an object without recorded digests, or
+  // a copy that cannot be patched shard by shard takes the rewrite route:
+  // get the object, overlay the range, put it back with replace=true.
+  // Replicas whose patched digests disagree: CHECKSUM_MISMATCH, nothing
+  // written. A write that fails midway leaves torn bytes: the key is
+  // cancelled (removed), as after a failed in-place upsert.
+  Result<void> patch(const ObjectKey& key, uint64_t offset, const void* data,
+                     uint64_t size);
+  // the two keystone calls behind patch (GpuClient's ranged paths use them)
+  Result<BatchGetWorkersResponse> patch_start(const std::vector<ObjectKey>& keys);
+  void patch_abort(const std::vector<ObjectKey>& keys);  // best effort
   Result<bool> exists(const ObjectKey& key);
   Result<void> remove(const ObjectKey& key);
   Result<uint64_t> remove_all();

@@ -159,6 +159,56 @@ class GpuClient {
   uint64_t striped_fused_items() const { return striped_fused_items_; }
   uint64_t striped_fused_get_items() const { return striped_fused_get_items_; }
 
+  // ---- ranged access ----
+  // A byte range of an object, to or from a device buffer.
+  struct DevRangeGet {
+    ObjectKey key;
+    uint64_t offset;
+    void* ptr;
+    uint64_t length;
+  };
+  struct DevRangePatch {
+    ObjectKey key;
+    uint64_t offset;
+    const void* ptr;
+    uint64_t length;
+  };
+  // Ranged gets: one BATCH_GET_WORKERS, then ONE gpu::batched_copy launch
+  // over the pieces that lie in device-visible shards (any offset and
+  // length inside the object); pieces of other shards are staged — the whole
+  // shard where it fits the staging buffer, then the slice. The first copy
+  // that covers the object serves an item; a failed staged read moves on to
+  // the next. UNVERIFIED: no recorded digest covers a range. A range that
+  // leaves its object is INVALID_ARGUMENT for that item.
+  Result<std::vector<int32_t>> batch_get_device_range(
+      const std::vector<DevRangeGet>& items);
+  Result<void> get_device_range(const ObjectKey& key, uint64_t offset,
+                                void* dev_ptr, uint64_t length);
+  // In-place range patches: one BATCH_PATCH_START, then ONE gpu::fused_patch
+  // launch over all items and all their copies — it writes the new bytes
+  // over the old ones and moves every shard digest and object checksum by
+  // the patched tiles' terms — then one BATCH_PUT_COMPLETE. Copies of an
+  // item whose new object digests disagree had diverged: CHECKSUM_MISMATCH,
+  // and the key is cancelled (its bytes are already written). A failed
+  // launch cancels every item that rode it (torn bytes, as after a failed
+  // in-place upsert). An item that cannot be patched in place — no recorded
+  // checksum or shard digest, a range that is not whole 1 KiB tiles (but for
+  // one ending at the object's end), a copy gpu::plan_patch refuses, a shard
+  // or a source that is not a 16B-aligned device-visible pointer — takes the
+  // REWRITE route: its patch start is aborted, the whole object is fetched
+  // (verified) into a temporary device buffer, the range overlaid and the
+  // object put back with replace=true; right on every tier and placement.
+  // The patched keys leave this client's placement cache, which also ends
+  // every session bound to them; other clients' cached verified gets
+  // mismatch and fall back to the RPC path.
+  Result<std::vector<int32_t>> batch_patch_device(
+      const std::vector<DevRangePatch>& items);
+  Result<void> patch_device(const ObjectKey& key, uint64_t offset,
+                            const void* dev_ptr, uint64_t length);
+  // items patched by the fused_patch launch / by the rewrite route
+  uint64_t patched_fused_items() const { return patched_fused_items_; }
+  uint64_t patched_rewrite_items() const { return patched_rewrite_items_; }
+
   // ---- pipelined batches: begin returns a token immediately; the batch
   // runs on a background thread (metadata RPCs of batch N+1 overlap the
   // GPU transfers of batch N — the single-client equivalent of running
@@ -296,6 +346,11 @@ class GpuClient {
   std::atomic<uint64_t> session_graph_steps_{0};
   std::atomic<uint64_t> striped_fused_items_{0};
   std::atomic<uint64_t> striped_fused_get_items_{0};
+  std::atomic<uint64_t> patched_fused_items_{0};
+  std::atomic<uint64_t> patched_rewrite_items_{0};
+  // the rewrite route of one patch item (info: what the keystone holds)
+  Result<void> patch_by_rewrite(const DevRangePatch& item,
+                                const GetWorkersResponse& info);
   // run the session desc list: captured-graph replay when available,
   // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
   // or a failed capture pins the session to the launch path)

@@ -236,6 +236,12 @@ struct ObjectMeta {
   uint32_t replication = 1;    // desired copy count (repair target)
   uint64_t last_scrub_ms = 0;  // when the scrubber last verified the digests
   ObjectState state = ObjectState::PENDING;
+  // When a patch start turned the object PENDING (checksum and shard
+  // digests kept; a patch abort puts it back to COMMITTED), 0 otherwise.
+  // Keystone-local, never on the wire. The abandoned-put reclaim counts
+  // from here: created_ms stays what it was, so that an abort restores it.
+  // (Next to `state`: a commit reads it where it stores anyway.)
+  uint64_t patch_started_ms = 0;
   std::vector<CopyPlacement> copies;
 
   bool expired(uint64_t now) const {

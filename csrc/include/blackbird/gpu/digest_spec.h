@@ -78,4 +78,26 @@ BB_HD constexpr uint64_t finalize(uint64_t h, uint64_t nbytes) {
   return mix64(h ^ nbytes);
 }
 
+// mix64 is a bijection of u64 (xorshifts by >= 32 are involutions, the
+// multipliers are odd), so a recorded digest gives its sum H back: what an
+// in-place patch adds its tiles' term differences to (patch_plan.h).
+constexpr uint64_t kUnmixMul1 = 0x9CB4B2F8129337DBull;  // 0xC4CEB9FE1A85EC53^-1
+constexpr uint64_t kUnmixMul2 = 0x4F74430C22A54005ull;  // 0xFF51AFD7ED558CCD^-1
+static_assert(kUnmixMul1 * 0xC4CEB9FE1A85EC53ull == 1);
+static_assert(kUnmixMul2 * 0xFF51AFD7ED558CCDull == 1);
+
+BB_HD constexpr uint64_t unmix64(uint64_t x) {
+  x = (x ^ (x >> 33)) * kUnmixMul1;
+  x = (x ^ (x >> 33)) * kUnmixMul2;
+  return x ^ (x >> 33);
+}
+
+BB_HD constexpr uint64_t unfinalize(uint64_t digest, uint64_t nbytes) {
+  return unmix64(digest) ^ nbytes;
+}
+
+static_assert(unmix64(mix64(0x0123456789ABCDEFull)) == 0x0123456789ABCDEFull);
+static_assert(mix64(unmix64(~0ull)) == ~0ull);
+static_assert(unfinalize(finalize(0xB1ACB19Dull, 3849), 3849) == 0xB1ACB19Dull);
+
 }  // namespace blackbird::digest

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "blackbird/common/result.h"
+#include "blackbird/gpu/patch_plan.h"
 #include "blackbird/gpu/stripe_plan.h"
 
 // Forward decl to avoid pulling hip_runtime into every TU.
@@ -46,6 +47,10 @@ uint64_t checksum_cpu(const void* ptr, uint64_t nbytes);
 uint64_t checksum_cpu_tiles(const void* chunk, uint64_t nbytes,
                             uint64_t first_tile);
 uint64_t checksum_cpu_finalize(uint64_t h, uint64_t object_nbytes);
+// The sum H a recorded digest was finalized from: what a range patch adds
+// checksum_cpu_tiles(new) - checksum_cpu_tiles(old) to before it finalizes
+// again (patch_plan.h).
+uint64_t checksum_cpu_unfinalize(uint64_t digest, uint64_t object_nbytes);
 
 // Waves the batched digest/fused kernels launch for a batch of total_tiles
 // 1-KiB tiles; each owns one contiguous range of ceil(total_tiles / waves)
@@ -101,6 +106,31 @@ Result<void> fused_stripe(const StripeSeg* segs, uint32_t nseg,
                           const uint64_t* obj_sizes, uint32_t nobj,
                           uint64_t* out_seg_digests, uint64_t* out_obj_digests,
                           hipStream_t stream);
+
+// Fused in-place range patch: overwrite every run's bytes at dst with the
+// new bytes at src (both device-visible, 16B-aligned) AND move the recorded
+// digests of the shards and objects the runs name, reading only the patched
+// tiles — old and new once each. out_shard_digests[i] is
+// finalize(unfinalize(shard_old[i], shard_lens[i]) + Σ term(new tiles) −
+// Σ term(old tiles), shard_lens[i]) over the runs naming shard i, slots
+// counted from the shard's start; out_obj_digests likewise with slots counted
+// from the object's start. A shard or object no run names keeps its digest.
+// When the bytes outside the runs are what the old digests were taken over,
+// these are the bbhash64 digests of the patched shards and objects; when they
+// are not, the new digests are as wrong as the old ones were. The arguments
+// go through check_patch_segs (patch_plan.h) before any HIP call. All arrays
+// are HOST arrays (call blocks on `stream`; nullptr = a stream of the shared
+// transfer pool). After an error past the check, the runs' bytes are torn.
+Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
+                         const uint64_t* shard_lens, const uint64_t* shard_old,
+                         uint32_t nshard, const uint64_t* obj_sizes,
+                         const uint64_t* obj_old, uint32_t nobj,
+                         uint64_t* out_shard_digests, uint64_t* out_obj_digests,
+                         hipStream_t stream);
+// Depth of fused_patch's load pipeline, per stream (old and new): a run of
+// full tiles enters its steady loop from 3 * depth tiles on. For tests to
+// size themselves, as digest_walk_depth.
+int patch_walk_depth();
 
 // Pre-instantiated fused-put step for batch sessions (fixed desc list every
 // step): descriptors live on-device (uploaded once by build), and the whole

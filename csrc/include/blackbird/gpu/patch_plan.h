@@ -1,0 +1,152 @@
+// Host-side rules of the in-place range patch (gpu::fused_patch,
+// csrc/hip/patch.hip), the twin of stripe_plan.h: the run descriptor, the
+// argument check and the planners that turn a byte range of one copy into
+// per-shard pieces. Pure host code, no HIP types — the clients, the bindings
+// and the tests use it without a GPU.
+//
+// bbhash64 is a commutative u64 sum H of per-tile terms, recorded as
+// mix64(H ^ nbytes) with mix64 a bijection (digest_spec.h). Overwriting
+// whole tiles in place therefore moves a digest by the difference of the
+// tiles' terms alone:
+//   new = finalize(unfinalize(old, n) + Σ term(new tiles) − Σ term(old tiles), n)
+// and only the patched tiles are read. Bytes outside the range are never
+// re-hashed, so a corrupt byte there stays detectable after the patch.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <optional>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "blackbird/common/result.h"
+#include "blackbird/gpu/digest_spec.h"
+#include "blackbird/gpu/stripe_plan.h"
+
+namespace blackbird::gpu {
+
+// One contiguous run of new bytes, written over the old ones at dst.
+struct PatchSeg {
+  const void* src;      // the new bytes
+  void* dst;            // the run's first byte in the pool
+  uint64_t nbytes;
+  uint64_t shard_tile;  // the run's first 1 KiB tile, counted in its SHARD
+  uint64_t obj_tile;    // ... and counted in its OBJECT
+  uint32_t shard;       // index into the shard arrays
+  uint32_t obj;         // index into the object arrays
+};
+
+// INVALID_ARGUMENT unless: every index is in range; every run lies inside
+// its shard and its object and covers whole tiles of both — only a run that
+// ends exactly at its object's end, which must be its shard's end too, may
+// end mid-tile (only there does the spec zero-pad); src and dst are 16-byte
+// aligned and [src, src+n) does not overlap [dst, dst+n); no two runs cover
+// the same tile of the same shard (the bytes left behind and the old terms
+// subtracted would depend on wave order); and no old digest is 0, which
+// means "not recorded". Zero-length runs are legal.
+inline Result<void> check_patch_segs(const PatchSeg* segs, uint32_t nseg,
+                                     const uint64_t* shard_lens,
+                                     const uint64_t* shard_old, uint32_t nshard,
+                                     const uint64_t* obj_sizes,
+                                     const uint64_t* obj_old, uint32_t nobj) {
+  using digest::kTileBytes;
+  auto bad = [](uint32_t i, const char* what) {
+    return Error{ErrorCode::INVALID_ARGUMENT,
+                 "patch run " + std::to_string(i) + ": " + what};
+  };
+  for (uint32_t i = 0; i < nshard; ++i)
+    if (shard_old[i] == 0)
+      return Error{ErrorCode::INVALID_ARGUMENT,
+                   "patch shard " + std::to_string(i) + ": no recorded digest"};
+  for (uint32_t i = 0; i < nobj; ++i)
+    if (obj_old[i] == 0)
+      return Error{ErrorCode::INVALID_ARGUMENT,
+                   "patch object " + std::to_string(i) + ": no recorded digest"};
+  // (shard, first tile, tile count, run) of the non-empty runs
+  std::vector<std::tuple<uint32_t, uint64_t, uint64_t, uint32_t>> cover;
+  for (uint32_t i = 0; i < nseg; ++i) {
+    const PatchSeg& s = segs[i];
+    if (s.shard >= nshard) return bad(i, "shard index out of range");
+    if (s.obj >= nobj) return bad(i, "object index out of range");
+    const uint64_t slen = shard_lens[s.shard];
+    const uint64_t size = obj_sizes[s.obj];
+    // tile*1024 + nbytes <= length, without overflow
+    if (s.shard_tile > slen / kTileBytes) return bad(i, "starts past its shard");
+    if (s.obj_tile > size / kTileBytes) return bad(i, "starts past its object");
+    const uint64_t sbegin = s.shard_tile * kTileBytes;
+    const uint64_t obegin = s.obj_tile * kTileBytes;
+    if (s.nbytes > slen - sbegin) return bad(i, "runs past its shard");
+    if (s.nbytes > size - obegin) return bad(i, "runs past its object");
+    if (s.nbytes % kTileBytes != 0 &&
+        (obegin + s.nbytes != size || sbegin + s.nbytes != slen))
+      return bad(i, "partial tile inside its object");
+    if (s.nbytes == 0) continue;
+    const uint64_t a = reinterpret_cast<uint64_t>(s.src);
+    const uint64_t b = reinterpret_cast<uint64_t>(s.dst);
+    if (a % 16 != 0 || b % 16 != 0) return bad(i, "address not 16-byte aligned");
+    if (s.nbytes > ~a || s.nbytes > ~b) return bad(i, "address range wraps");
+    if (a < b + s.nbytes && b < a + s.nbytes)
+      return bad(i, "source overlaps destination");
+    cover.emplace_back(s.shard, s.shard_tile,
+                       (s.nbytes + kTileBytes - 1) / kTileBytes, i);
+  }
+  std::sort(cover.begin(), cover.end());
+  for (size_t k = 1; k < cover.size(); ++k) {
+    const auto& [ps, pt, pn, pi] = cover[k - 1];
+    const auto& [cs, ct, cn, ci] = cover[k];
+    if (ps == cs && ct < pt + pn) return bad(ci, "covers a tile of another run");
+  }
+  return {};
+}
+
+// What a byte range touches of one shard of a copy.
+struct RangePiece {
+  uint32_t shard;      // index into the copy's shards
+  uint64_t shard_off;  // byte offset in the shard
+  uint64_t obj_off;    // byte offset in the object
+  uint64_t nbytes;
+};
+
+// The pieces of [offset, offset+length) of a copy whose shards hold the
+// object's bytes back to back, in shard order; any offset and length inside
+// the object (what a ranged get needs). nullopt: the lengths do not add up
+// to the object, or the range leaves it. An empty range has no piece.
+inline std::optional<std::vector<RangePiece>> range_pieces(
+    uint64_t obj_size, const std::vector<uint64_t>& shard_lens, uint64_t offset,
+    uint64_t length) {
+  if (offset > obj_size || length > obj_size - offset) return std::nullopt;
+  std::vector<RangePiece> out;
+  const uint64_t end = offset + length;
+  uint64_t off = 0;
+  for (size_t i = 0; i < shard_lens.size(); ++i) {
+    const uint64_t len = shard_lens[i];
+    if (len > obj_size - off) return std::nullopt;
+    const uint64_t lo = std::max(off, offset);
+    const uint64_t hi = std::min(off + len, end);
+    if (lo < hi)
+      out.push_back({static_cast<uint32_t>(i), lo - off, lo, hi - lo});
+    off += len;
+  }
+  if (off != obj_size) return std::nullopt;
+  return out;
+}
+
+// The same for an in-place patch: every piece is a legal PatchSeg once it has
+// addresses (shard_tile = shard_off / 1024, obj_tile = obj_off / 1024).
+// nullopt ("rewrite the object instead"): plan_stripe refuses the copy, the
+// offset is not a multiple of 1024, or the length is not and the range does
+// not end at the object's end.
+inline std::optional<std::vector<RangePiece>> plan_patch(
+    uint64_t obj_size, const std::vector<uint64_t>& shard_lens, uint64_t offset,
+    uint64_t length) {
+  using digest::kTileBytes;
+  if (!plan_stripe(obj_size, shard_lens)) return std::nullopt;
+  if (offset % kTileBytes != 0) return std::nullopt;
+  if (offset > obj_size || length > obj_size - offset) return std::nullopt;
+  if (length % kTileBytes != 0 && offset + length != obj_size)
+    return std::nullopt;
+  return range_pieces(obj_size, shard_lens, offset, length);
+}
+
+}  // namespace blackbird::gpu

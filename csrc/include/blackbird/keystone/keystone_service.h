@@ -64,6 +64,23 @@ class KeystoneService {
   std::vector<uint8_t> batch_object_exists(const std::vector<ObjectKey>& keys);
   std::vector<int32_t> batch_remove(const std::vector<ObjectKey>& keys);
 
+  // ---- in-place range patches ----
+  // BATCH_PATCH_START: every key that is COMMITTED, unexpired and has a
+  // recorded checksum turns PENDING, which pins its placements exactly as an
+  // in-place upsert does — but checksum and shard digests are KEPT: the
+  // client moves them by the patched tiles' terms (gpu/patch_plan.h) and
+  // commits through batch_put_complete / put_complete, which restarts the
+  // TTL as for an upsert. The answer carries size, checksum and copies with
+  // shard digests. Any other key gets a status (INVALID_STATE: no recorded
+  // checksum) and keeps its state.
+  BatchGetWorkersResponse batch_patch_start(const std::vector<ObjectKey>& keys);
+  // BATCH_PATCH_ABORT, for a client that has written nothing: a key PENDING
+  // from a patch start goes back to COMMITTED with checksum, digests and
+  // clocks untouched; any other key gets INVALID_STATE. After a launch that
+  // failed midway the bytes are torn and the route is put_cancel, which
+  // removes the key — the contract of a failed in-place upsert.
+  std::vector<int32_t> batch_patch_abort(const std::vector<ObjectKey>& keys);
+
   // ---- sessionful upserts (steady-state small-object fast path) ----
   // A put session pins an ordered key list server-side so repeat puts of the
   // same batch cost two tiny RPCs: upsert_start_token (flip every object to

@@ -47,6 +47,11 @@ constexpr uint16_t BATCH_COMMIT_TOKEN = 27;
 // commits every step with the object digests AND each shard's own digest
 constexpr uint16_t BATCH_SESSION_OPEN = 28;
 constexpr uint16_t BATCH_COMMIT_TOKEN_SHARDS = 29;
+// in-place range patches: start pins the keys PENDING with their digests
+// kept and answers as BATCH_GET_WORKERS does; the commit is
+// BATCH_PUT_COMPLETE; abort puts an unwritten key back to COMMITTED
+constexpr uint16_t BATCH_PATCH_START = 30;
+constexpr uint16_t BATCH_PATCH_ABORT = 31;
 
 // worker data plane (TCP fallback path; SHM/HIP-IPC paths bypass RPC)
 constexpr uint16_t DATA_WRITE = 200;

@@ -26,9 +26,10 @@ void KeystoneService::run_gc_once() {
   std::vector<ObjectKey> dead;
   for (const auto& [key, meta] : objects_) {
     if (meta.expired(now)) dead.push_back(key);
-    // abandoned PENDING puts: reclaim after 10 minutes
+    // abandoned PENDING puts: reclaim after 10 minutes (a patch start
+    // keeps created_ms, its own clock counts)
     else if (meta.state == ObjectState::PENDING &&
-             now > meta.created_ms + 600000)
+             now > std::max(meta.created_ms, meta.patch_started_ms) + 600000)
       dead.push_back(key);
   }
   for (const auto& k : dead) remove_object_locked(k);

@@ -162,6 +162,16 @@ void KeystoneServer::register_handlers() {
     if (!r.ok()) return r.error();
     return serde::to_bytes(ks.batch_get_workers(r->keys));
   });
+  leader_only(M::BATCH_PATCH_START, [&ks](const std::string& b, const Ctx&) -> Reply {
+    auto r = decode<KeysMsg>(b);
+    if (!r.ok()) return r.error();
+    return serde::to_bytes(ks.batch_patch_start(r->keys));
+  });
+  leader_only(M::BATCH_PATCH_ABORT, [&ks](const std::string& b, const Ctx&) -> Reply {
+    auto r = decode<KeysMsg>(b);
+    if (!r.ok()) return r.error();
+    return serde::to_bytes(StatusListMsg{ks.batch_patch_abort(r->keys)});
+  });
   // ---- compact v2 batch protocol: pool-table + fixed-width placements ----
   leader_only(M::BATCH_PUT_START2, [&ks](const std::string& b, const Ctx&) -> Reply {
     auto rq = wire::decode_put_start2_request(b);

@@ -178,6 +178,7 @@ inline void publish_commit(ObjectMeta& m, uint64_t checksum, uint64_t now) {
   rstore(m.checksum, checksum);
   rstore(m.created_ms, now);
   rstore(m.last_access_ms, now);
+  if (rload(m.patch_started_ms) != 0) rstore(m.patch_started_ms, uint64_t{0});
   std::atomic_ref<ObjectState>(m.state).store(ObjectState::COMMITTED, std::memory_order_release);
 }
 
@@ -619,6 +620,62 @@ std::vector<int32_t> KeystoneService::batch_remove(
   // range frees take only the allocator's own lock — once for the batch
   allocator_.free_batch(to_free);
   flush_dirty_now();  // deletions durable before the reply (retry-safe)
+  return out;
+}
+
+// ------------------------------------------------- in-place range patches
+
+BatchGetWorkersResponse KeystoneService::batch_patch_start(
+    const std::vector<ObjectKey>& keys) {
+  BatchGetWorkersResponse out;
+  out.items.resize(keys.size());
+  if (!is_leader()) {
+    for (auto& it : out.items)
+      it.status = static_cast<int32_t>(ErrorCode::NOT_LEADER);
+    return out;
+  }
+  const uint64_t now = now_ms();
+  // exclusive, as every COMMITTED -> PENDING flip (admit_locked)
+  std::unique_lock lk(objects_mu_);
+  for (size_t i = 0; i < keys.size(); ++i) {
+    auto& item = out.items[i];
+    auto it = objects_.find(keys[i]);
+    ObjectMeta* m = it == objects_.end() ? nullptr : &it->second;
+    ErrorCode status = readable(m, now);
+    if (status == ErrorCode::OK && m->checksum == 0)
+      status = ErrorCode::INVALID_STATE;  // nothing to move
+    item.status = static_cast<int32_t>(status);
+    if (status == ErrorCode::OBJECT_EXPIRED) remove_object_locked(keys[i]);
+    if (status != ErrorCode::OK) continue;
+    fill_info(item.info, *m);
+    m->patch_started_ms = now ? now : 1;
+    m->state = ObjectState::PENDING;
+  }
+  return out;
+}
+
+std::vector<int32_t> KeystoneService::batch_patch_abort(
+    const std::vector<ObjectKey>& keys) {
+  std::vector<int32_t> out(keys.size(), 0);
+  if (!is_leader()) {
+    out.assign(keys.size(), static_cast<int32_t>(ErrorCode::NOT_LEADER));
+    return out;
+  }
+  std::unique_lock lk(objects_mu_);
+  for (size_t i = 0; i < keys.size(); ++i) {
+    auto it = objects_.find(keys[i]);
+    if (it == objects_.end()) {
+      out[i] = static_cast<int32_t>(ErrorCode::OBJECT_NOT_FOUND);
+      continue;
+    }
+    ObjectMeta& m = it->second;
+    if (m.state != ObjectState::PENDING || m.patch_started_ms == 0) {
+      out[i] = static_cast<int32_t>(ErrorCode::INVALID_STATE);
+      continue;
+    }
+    m.patch_started_ms = 0;
+    m.state = ObjectState::COMMITTED;
+  }
   return out;
 }
 
