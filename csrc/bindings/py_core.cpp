@@ -602,16 +602,19 @@ PYBIND11_MODULE(_core, m) {
                     reinterpret_cast<void*>(dst), n});
     return ds;
   };
-  gm.def("fused_put", [to_put_descs](const DescTuples& descs) {
+  // warm_bytes / warm_loads: gpu::WarmTail
+  gm.def("fused_put", [to_put_descs](const DescTuples& descs,
+                                     uint64_t warm_bytes, bool warm_loads) {
     auto ds = to_put_descs(descs);
     // poisoned: finalize(0, 0) is 0, so a digest that was never written
     // must not pass for the digest of an empty object
     std::vector<uint64_t> out(ds.size(), ~0ull);
     py::gil_scoped_release rel;
     unwrap_void(gpu::fused_put(ds.data(), static_cast<uint32_t>(ds.size()),
-                               out.data(), nullptr));
+                               out.data(), nullptr, {warm_bytes, warm_loads}));
     return out;
-  });
+  }, py::arg("descs"), py::arg("warm_bytes") = 0,
+     py::arg("warm_loads") = false);
   // striped copy+digest: segs are (src, dst, nbytes, first_tile, obj) tuples;
   // returns (segment digests, object digests)
   using SegTuples =
@@ -725,19 +728,31 @@ PYBIND11_MODULE(_core, m) {
     return to_piece_tuples(gpu::range_pieces(obj_size, shard_lens, offset, length));
   }, py::arg("obj_size"), py::arg("shard_lens"), py::arg("offset"),
      py::arg("length"));
-  // one FusedPutPlan, replayed `steps` times: one digest list per step
+  // one FusedPutPlan, replayed `steps` times: one digest list per step.
+  // before_step(k), when given, runs before replay k, as in
+  // fused_stripe_plan below.
   gm.def("fused_put_plan",
-         [to_put_descs](const DescTuples& descs, int steps, int device) {
+         [to_put_descs](const DescTuples& descs, int steps, int device,
+                        uint64_t warm_bytes, bool warm_loads,
+                        py::object before_step) {
            auto ds = to_put_descs(descs);
            std::vector<std::vector<uint64_t>> out(
                steps, std::vector<uint64_t>(ds.size()));
-           py::gil_scoped_release rel;
            gpu::FusedPutPlan plan;
-           unwrap_void(plan.build(ds.data(), static_cast<uint32_t>(ds.size()),
-                                  device));
-           for (auto& step : out) unwrap_void(plan.run(step.data()));
+           {
+             py::gil_scoped_release rel;
+             unwrap_void(plan.build(ds.data(), static_cast<uint32_t>(ds.size()),
+                                    device, {warm_bytes, warm_loads}));
+           }
+           for (int k = 0; k < steps; ++k) {
+             if (!before_step.is_none()) before_step(k);
+             py::gil_scoped_release rel;
+             unwrap_void(plan.run(out[k].data()));
+           }
            return out;
-         }, py::arg("descs"), py::arg("steps"), py::arg("device") = 0);
+         }, py::arg("descs"), py::arg("steps"), py::arg("device") = 0,
+         py::arg("warm_bytes") = 0, py::arg("warm_loads") = false,
+         py::arg("before_step") = py::none());
   // one FusedStripePlan, replayed `steps` times: one (segment digests, object
   // digests) pair per step, poisoned before each run as in fused_stripe.
   // before_step(k), when given, runs before replay k (a test rewrites the

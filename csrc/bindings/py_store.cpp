@@ -511,6 +511,9 @@ void bind_store(py::module_& m) {
       .def("init", [](GpuClient& g) { unwrap_void(g.init()); },
            py::call_guard<py::gil_scoped_release>())
       .def("set_fused_copy", &GpuClient::set_fused_copy)
+      .def("set_warm_tail_bytes", &GpuClient::set_warm_tail_bytes,
+           py::arg("bytes"))
+      .def_property_readonly("warm_tail_bytes", &GpuClient::warm_tail_bytes)
       .def("put_device", [](GpuClient& g, const std::string& key, uint64_t ptr,
                             uint64_t size, const PlacementConfig& cfg) {
         unwrap_void(g.put_device(key, reinterpret_cast<const void*>(ptr), size, cfg));

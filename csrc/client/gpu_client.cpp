@@ -218,7 +218,8 @@ struct GpuClient::Router {
     std::vector<uint64_t> digests(hashed.size(), 0);
     BB_RETURN_IF_ERROR(gpu::fused_put(hashed.data(),
                                       static_cast<uint32_t>(hashed.size()),
-                                      digests.data(), g.streams_[2]));
+                                      digests.data(), g.streams_[2],
+                                      g.warm_tail(Put)));
     return digests;
   }
   // Everything a put batch launches, in order: the copy list (stream 0), one
@@ -915,12 +916,14 @@ Result<void> GpuClient::patch_device(const ObjectKey& key, uint64_t offset,
 // Pool-table responses with fixed-width placements: the client resolves each
 // POOL once (not each object) and decodes with zero per-item allocations.
 
-Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests) {
+Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests,
+                                       bool put) {
   static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
   if (!no_graph && !sess.plan && !sess.plan_failed) {
     auto plan = std::make_shared<gpu::FusedPutPlan>();
     auto rb = plan->build(sess.descs.data(),
-                          static_cast<uint32_t>(sess.descs.size()), device_);
+                          static_cast<uint32_t>(sess.descs.size()), device_,
+                          warm_tail(put));
     if (rb.ok()) {
       sess.plan = std::move(plan);
     } else {
@@ -941,7 +944,7 @@ Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests) {
   }
   return gpu::fused_put(sess.descs.data(),
                         static_cast<uint32_t>(sess.descs.size()), digests,
-                        streams_[2]);
+                        streams_[2], warm_tail(put));
 }
 
 Result<void> GpuClient::session_stripe_kernel(SessionCore& sess,
@@ -1010,7 +1013,7 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
     return std::nullopt;
   }
   std::vector<uint64_t> digests(sess->descs.size(), 0);
-  auto rk = session_kernel(*sess, digests.data());
+  auto rk = session_kernel(*sess, digests.data(), /*put=*/true);
   if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
   // keep the session for the next step; one digest per ITEM (replicas hash
   // identical bytes; take copy 0's)
@@ -1291,7 +1294,7 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     }
   BB_TRACE_SCOPE("bb::session_get");
   std::vector<uint64_t> got(items.size(), 0);
-  auto rk = session_kernel(*sess, got.data());
+  auto rk = session_kernel(*sess, got.data(), /*put=*/false);
   if (!rk.ok()) return {rk.error()};
   std::vector<uint32_t> miss;
   for (size_t j = 0; j < items.size(); ++j)
@@ -1402,7 +1405,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
     BB_TRACE_SCOPE("bb::cached_get");
     std::vector<uint64_t> got(descs.size(), 0);
     auto r = gpu::fused_put(descs.data(), static_cast<uint32_t>(descs.size()),
-                            got.data(), streams_[2]);
+                            got.data(), streams_[2], warm_tail(/*put=*/false));
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(stripes.run(streams_[2]));
     striped_fused_get_items_.fetch_add(stripes.entries.size());

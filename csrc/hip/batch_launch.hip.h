@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 
 #include "blackbird/gpu/gpu_kernels.h"
@@ -62,16 +63,22 @@ inline int digest_grid(uint64_t total_tiles) {
 __global__ void bbhash64_batch_kernel(const CopyDesc*, const uint64_t*, uint32_t,
                                       uint64_t, unsigned long long*);
 __global__ void fused_put_kernel(const CopyDesc*, const uint64_t*, uint32_t,
-                                 uint64_t, unsigned long long*);
+                                 uint64_t, unsigned long long*, uint64_t);
+__global__ void fused_get_kernel(const CopyDesc*, const uint64_t*, uint32_t,
+                                 uint64_t, unsigned long long*, uint64_t);
 __global__ void bbhash64_finalize_kernel(const CopyDesc*, uint32_t,
                                          unsigned long long*);
 
 // The digest step over an uploaded block: zero the accumulators → hash
 // (kCopy: and copy) every tile → finalize per object → digests to host_out
 // (pinned). Only enqueues; the caller synchronizes or captures `stream`.
+// kCopy: the last warm.bytes of the batch, in whole tiles, are its warm tail
+// (gpu_kernels.h, WarmTail); this is the one place that turns them into the
+// kernels' tile index.
 template <bool kCopy>
 Result<void> enqueue_digest(void* device_block, uint32_t n, uint64_t total_tiles,
-                            uint64_t* host_out, hipStream_t stream) {
+                            uint64_t* host_out, hipStream_t stream,
+                            WarmTail warm = {}) {
   const BatchBlock b{n};
   const CopyDesc* d_descs = b.descs(device_block);
   const uint64_t* d_prefix = b.prefix(device_block);
@@ -80,9 +87,18 @@ Result<void> enqueue_digest(void* device_block, uint32_t n, uint64_t total_tiles
   if (total_tiles > 0) {
     const int blocks = digest_grid(total_tiles);
     if constexpr (kCopy) {
-      fused_put_kernel<<<blocks, dev::kBlock, 0, stream>>>(d_descs, d_prefix, n,
-                                                           total_tiles, d_out);
-      BB_HIP_LAUNCHED("fused_put_kernel");
+      const uint64_t warm_tiles =
+          std::min<uint64_t>(total_tiles, warm.bytes / digest::kTileBytes);
+      const uint64_t warm_begin = total_tiles - warm_tiles;
+      if (warm.loads) {
+        fused_get_kernel<<<blocks, dev::kBlock, 0, stream>>>(
+            d_descs, d_prefix, n, total_tiles, d_out, warm_begin);
+        BB_HIP_LAUNCHED("fused_get_kernel");
+      } else {
+        fused_put_kernel<<<blocks, dev::kBlock, 0, stream>>>(
+            d_descs, d_prefix, n, total_tiles, d_out, warm_begin);
+        BB_HIP_LAUNCHED("fused_put_kernel");
+      }
     } else {
       bbhash64_batch_kernel<<<blocks, dev::kBlock, 0, stream>>>(
           d_descs, d_prefix, n, total_tiles, d_out);

@@ -40,12 +40,28 @@ bbhash64_batch_kernel(const CopyDesc* __restrict__ descs,
   digest_walk<false, 0>(descs, tile_prefix, nobjs, total_tiles, out);
 }
 
-// Fused put: copy src→dst and hash, reading the data once.
+// Fused put: copy src→dst and hash, reading the data once. The global tiles
+// from warm_begin on are stored plainly (digest_walk, kWarm); >= total_tiles:
+// none.
 __global__ void __launch_bounds__(kBlock)
 fused_put_kernel(const CopyDesc* __restrict__ descs,
                  const uint64_t* __restrict__ tile_prefix, uint32_t nobjs,
-                 uint64_t total_tiles, unsigned long long* __restrict__ out) {
-  digest_walk<true, kWalkDepth>(descs, tile_prefix, nobjs, total_tiles, out);
+                 uint64_t total_tiles, unsigned long long* __restrict__ out,
+                 uint64_t warm_begin) {
+  digest_walk<true, kWalkDepth, CopyDesc, true, kWarmStores>(
+      descs, tile_prefix, nobjs, total_tiles, out, nullptr, warm_begin);
+}
+
+// The same walk for the get that reads what such a put left on-die: the
+// global tiles from warm_begin on are loaded plainly, every store is
+// nontemporal.
+__global__ void __launch_bounds__(kBlock)
+fused_get_kernel(const CopyDesc* __restrict__ descs,
+                 const uint64_t* __restrict__ tile_prefix, uint32_t nobjs,
+                 uint64_t total_tiles, unsigned long long* __restrict__ out,
+                 uint64_t warm_begin) {
+  digest_walk<true, kWalkDepth, CopyDesc, true, kWarmLoads>(
+      descs, tile_prefix, nobjs, total_tiles, out, nullptr, warm_begin);
 }
 
 __global__ void bbhash64_finalize_kernel(const CopyDesc* __restrict__ descs,
@@ -120,13 +136,14 @@ thread_local DescStaging g_put_stage;
 template <bool kCopy>
 Result<void> digest_batch_sync(DescStaging& stage, const CopyDesc* descs,
                                uint32_t n, uint64_t* out_digests,
-                               hipStream_t stream) {
+                               hipStream_t stream, WarmTail warm = {}) {
   const BatchBlock b{n};
   const uint64_t total = fill_block(b, stage.pinned, descs, kTileBytes);
   BB_HIP_TRY(hipMemcpyAsync(stage.device, stage.pinned, b.upload_bytes(),
                             hipMemcpyHostToDevice, stream));
   uint64_t* h_out = b.out(stage.pinned);
-  BB_RETURN_IF_ERROR(enqueue_digest<kCopy>(stage.device, n, total, h_out, stream));
+  BB_RETURN_IF_ERROR(
+      enqueue_digest<kCopy>(stage.device, n, total, h_out, stream, warm));
   BB_HIP_TRY(hipStreamSynchronize(stream));
   std::memcpy(out_digests, h_out, b.out_bytes());
   return {};
@@ -190,10 +207,11 @@ Result<void> checksum_batch(const void* const* dev_ptrs, const uint64_t* sizes,
 }
 
 Result<void> fused_put(const PutDesc* descs, uint32_t n, uint64_t* out_digests,
-                       hipStream_t stream) {
+                       hipStream_t stream, WarmTail warm) {
   if (n == 0) return {};
   BB_RETURN_IF_ERROR(g_put_stage.acquire(BatchBlock{n}.bytes()));
-  return digest_batch_sync<true>(g_put_stage, descs, n, out_digests, stream);
+  return digest_batch_sync<true>(g_put_stage, descs, n, out_digests, stream,
+                                 warm);
 }
 
 // ----------------- hipGraph-replayed session step (FusedPutPlan) -----------
@@ -205,7 +223,8 @@ struct FusedPutPlan::Impl : GraphStep {};
 
 FusedPutPlan::~FusedPutPlan() { delete impl_; }
 
-Result<void> FusedPutPlan::build(const PutDesc* descs, uint32_t n, int device) {
+Result<void> FusedPutPlan::build(const PutDesc* descs, uint32_t n, int device,
+                                 WarmTail warm) {
   if (impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan already built"};
   if (n == 0) return Error{ErrorCode::INVALID_ARGUMENT, "empty desc list"};
   BB_HIP_TRY(hipSetDevice(device));
@@ -219,7 +238,7 @@ Result<void> FusedPutPlan::build(const PutDesc* descs, uint32_t n, int device) {
   BB_RETURN_IF_ERROR(impl->prepare(h_block.get(), b.upload_bytes(), b.bytes(),
                                    b.out_bytes()));
   BB_RETURN_IF_ERROR(impl->capture([&](hipStream_t s) {
-    return enqueue_digest<true>(impl->dev, n, total, impl->h_out, s);
+    return enqueue_digest<true>(impl->dev, n, total, impl->h_out, s, warm);
   }));
   n_ = n;
   impl_ = impl.release();

@@ -167,13 +167,20 @@ __device__ inline i32x4 load_a_frag(const uint8_t* tile_base, uint32_t lane_off)
   else return *p;
 }
 
+// kNt: the store is nontemporal, the default of every copying walk: what it
+// writes is not expected to be read soon. A plain store allocates in the
+// 256 MiB Infinity Cache, and measurably so (profiles/warm_tail_checks.md):
+// on the 512 x 1 MiB put, the last 128 MiB stored plainly make that launch
+// 9 us shorter and, loaded plainly, the get behind it 9 us shorter; with two
+// lanes the pair gains 5 %. Stored plainly throughout, the put is 23 us
+// shorter and the get no faster than cold: the batch evicts itself. Hence
+// the walk's warm tail (digest_walk, kWarm), and nontemporal everywhere else.
+template <bool kNt = true>
 __device__ inline void store_a_frag(uint8_t* tile_base, uint32_t lane_off,
                                     const i32x4& a) {
-  // nontemporal: an A/B test against a temporal (L2-filling) store was
-  // within run variance end-to-end; the 1000-step soak record stands on
-  // this version
-  __builtin_nontemporal_store(
-      a, (global_ptr<i32x4>)(as_global(tile_base) + lane_off));
+  const auto p = (global_ptr<i32x4>)(as_global(tile_base) + lane_off);
+  if constexpr (kNt) __builtin_nontemporal_store(a, p);
+  else *p = a;
 }
 
 // The tail tile: bytes at and past nbytes read as zero ...
@@ -236,6 +243,11 @@ constexpr int kWalkDepth = 4;
 // Longest run of full tiles the walk takes in one go (1 TiB).
 constexpr uint32_t kMaxRun = 1u << 30;
 
+// What a wave of the walk's warm tail does plainly (digest_walk, kWarm).
+constexpr int kWarmNone = 0;
+constexpr int kWarmStores = 1;
+constexpr int kWarmLoads = 2;
+
 // The batched tile walk. One desc = one contiguous run of bytes that starts
 // on a tile boundary: a whole object at object-offset 0 (CopyDesc), or a
 // segment of a striped object (StripeSeg). tile_prefix[i] is the global index
@@ -266,11 +278,21 @@ constexpr uint32_t kMaxRun = 1u << 30;
 //              the 512 × 1 MiB put it is worth 3–5 % of the launch
 //              (profiles/walk_persistent_checks.md). The hash-only walk was
 //              not measured with it and loads plainly.
-template <bool kCopy, int kDepth, typename Desc, bool kNtLoads = kCopy>
+//   kWarm:     the walk has a warm tail, the global tiles from warm_begin on
+//              (>= total_tiles: none). A wave whose range begins there
+//              accesses its full tiles plainly, so that they allocate in the
+//              Infinity Cache: its stores with kWarmStores, its loads with
+//              kWarmLoads. The `nt` bit is an instruction modifier, so the
+//              run body exists twice behind one scalar branch per run; a
+//              boundary inside a wave's range rounds to the wave. Tail tiles
+//              keep their byte path. kWarmNone: no such branch, one body.
+template <bool kCopy, int kDepth, typename Desc, bool kNtLoads = kCopy,
+          int kWarm = kWarmNone>
 __device__ __forceinline__ void digest_walk(
     const Desc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
     uint32_t nobjs, uint64_t total_tiles, unsigned long long* __restrict__ out,
-    unsigned long long* __restrict__ obj_out = nullptr) {
+    unsigned long long* __restrict__ obj_out = nullptr,
+    uint64_t warm_begin = ~0ull) {
   constexpr bool kStripe = std::is_same_v<Desc, StripeSeg>;
   const int lane = threadIdx.x & 63;
   // the wave index and all that follows from it: ranges, boundaries and the
@@ -283,6 +305,7 @@ __device__ __forceinline__ void digest_walk(
   const uint64_t begin = gwave * per;
   const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
   if (begin >= total_tiles) return;
+  [[maybe_unused]] const bool warm = begin >= warm_begin;
 
   const i32x4 b_frag = load_b_frag(lane);
   const WReg wr = load_w_reg(lane);
@@ -330,19 +353,22 @@ __device__ __forceinline__ void digest_walk(
   };
   // n >= 1 full tiles of the current desc, from its tile t0. Counting inside
   // a run is 32-bit: scalar compares, where 64-bit ones take the VALU.
-  auto full_run = [&](uint64_t t0, uint32_t n) {
+  // warm_tag: the run belongs to a wave of the warm tail.
+  auto full_run = [&](auto warm_tag, uint64_t t0, uint32_t n) {
+    constexpr bool kWarmRun = decltype(warm_tag)::value;
+    constexpr bool kNtSt = !(kWarmRun && (kWarm & kWarmStores));
+    constexpr bool kNtLd = kNtLoads && !(kWarmRun && (kWarm & kWarmLoads));
     const uint8_t* s = src + t0 * kTileBytes;
     // the fragment's last uses: the store and the MFMA
     auto consume = [&](const i32x4& a, uint32_t i) {
       if constexpr (kCopy)
-        store_a_frag(dst + (t0 + i) * kTileBytes, lane_off, a);
+        store_a_frag<kNtSt>(dst + (t0 + i) * kTileBytes, lane_off, a);
       return project_tile(a, b_frag);
     };
     // tiles [i, stop) of the run one by one: load, consume, fold
     auto plain = [&](uint32_t i, uint32_t stop) {
       for (; i < stop; ++i)
-        fold(consume(load_a_frag<kNtLoads>(s + uint64_t{i} * kTileBytes,
-                                           lane_off),
+        fold(consume(load_a_frag<kNtLd>(s + uint64_t{i} * kTileBytes, lane_off),
                      i),
              t0 + i);
     };
@@ -365,7 +391,7 @@ __device__ __forceinline__ void digest_walk(
         const i32x16 acc = consume(buf[k], i + k);
         __builtin_amdgcn_sched_barrier(0);
         if (refill)
-          buf[k] = load_a_frag<kNtLoads>(
+          buf[k] = load_a_frag<kNtLd>(
               s + uint64_t{i + k + kDepth} * kTileBytes, lane_off);
         __builtin_amdgcn_sched_barrier(0);
         fold(acc, t0 + i + k);
@@ -373,7 +399,7 @@ __device__ __forceinline__ void digest_walk(
       };
 #pragma unroll
       for (uint32_t k = 0; k < kDepth; ++k) {
-        buf[k] = load_a_frag<kNtLoads>(s + uint64_t{k} * kTileBytes, lane_off);
+        buf[k] = load_a_frag<kNtLd>(s + uint64_t{k} * kTileBytes, lane_off);
         __builtin_amdgcn_sched_barrier(0);
       }
       // Steady state: every step issues one load. The first group stands in
@@ -414,7 +440,12 @@ __device__ __forceinline__ void digest_walk(
     if (t < full_stop) {
       const uint64_t left = full_stop - t;
       const uint32_t n = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
-      full_run(t, n);
+      if constexpr (kWarm != kWarmNone) {
+        if (warm) full_run(std::true_type{}, t, n);
+        else full_run(std::false_type{}, t, n);
+      } else {
+        full_run(std::false_type{}, t, n);
+      }
       gt += n;
     } else {
       // tail tile: zero-padded hash, byte-guarded store

@@ -228,6 +228,18 @@ class GpuClient {
   // (hipMemcpyAsync on rotating streams) for every transfer.
   void set_fused_copy(bool on) { fused_copy_ = on; }
 
+  // Warm-tail budget of the copy+digest launches (gpu::WarmTail): up to this
+  // many bytes at the end of every such put launch are stored so that they
+  // stay in the Infinity Cache, and a get loads the end of its batch to
+  // match: the get of a batch that this client has just put reads that much
+  // on-die. Bytes and digests do not depend on it. Striped and patch
+  // launches take none. A session's captured step keeps the budget it was
+  // built with. Default: what profiles/warm_tail_checks.md selected for two
+  // lanes, which between them keep 256 MiB, the size of the cache.
+  static constexpr uint64_t kDefaultWarmTailBytes = 128ull << 20;
+  void set_warm_tail_bytes(uint64_t bytes) { warm_tail_bytes_ = bytes; }
+  uint64_t warm_tail_bytes() const { return warm_tail_bytes_; }
+
   // ---- collective batch shuffle (RCCL over xGMI; see shuffle.h) ----
   // Every rank calls this together: want[p] lists the objects this rank
   // wants FROM rank p (received contiguously at want[p].recv_base). Served
@@ -354,7 +366,12 @@ class GpuClient {
   // run the session desc list: captured-graph replay when available,
   // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
   // or a failed capture pins the session to the launch path)
-  Result<void> session_kernel(SessionCore& sess, uint64_t* digests);
+  Result<void> session_kernel(SessionCore& sess, uint64_t* digests, bool put);
+  // The warm tail a copy+digest launch of this client asks for, decided here
+  // for every path: a put leaves its budget's worth of the batch on-die,
+  // and a get loads the same tail plainly (nontemporal loads of resident
+  // lines measured slower with two lanes, profiles/warm_tail_checks.md).
+  gpu::WarmTail warm_tail(bool put) const { return {warm_tail_bytes_, !put}; }
   // the same over a striped session's segment list (FusedStripePlan replay,
   // fused_stripe launches otherwise)
   Result<void> session_stripe_kernel(SessionCore& sess, uint64_t* seg_digests,
@@ -365,6 +382,7 @@ class GpuClient {
   std::optional<Result<std::vector<int32_t>>> try_striped_session_get(
       const std::vector<DevGetItem>& items, BatchGetSession* sess);
   bool fused_copy_ = true;
+  uint64_t warm_tail_bytes_ = kDefaultWarmTailBytes;
   bool initialized_ = false;
 };
 

@@ -90,8 +90,19 @@ Result<void> batched_copy(const CopyDesc* descs, uint32_t n, hipStream_t stream)
 // is read once instead of twice (copy + hash). out_digests: HOST array
 // (call blocks on `stream`).
 using PutDesc = CopyDesc;
+// The warm tail of a copy+digest batch: its last `bytes`, in whole tiles and
+// rounded down to whole per-wave ranges. A put (loads == false) stores the
+// tail plainly where all else is stored nontemporally, so that it stays in
+// the Infinity Cache; the get of the same batch shortly afterwards (loads ==
+// true) loads the tail plainly where all else is loaded nontemporally, and is
+// served on-die (KERNELS.md, "Store policy"). A residency hint: bytes and
+// digests do not depend on it. bytes 0: none; more than the batch: all of it.
+struct WarmTail {
+  uint64_t bytes = 0;
+  bool loads = false;
+};
 Result<void> fused_put(const PutDesc* descs, uint32_t n, uint64_t* out_digests,
-                       hipStream_t stream);
+                       hipStream_t stream, WarmTail warm = {});
 
 // Fused striped transfer: copy every segment src→dst (both device-visible,
 // 16B-aligned) AND compute, reading the data once, two digests — per segment
@@ -145,7 +156,9 @@ class FusedPutPlan {
   FusedPutPlan(const FusedPutPlan&) = delete;
   FusedPutPlan& operator=(const FusedPutPlan&) = delete;
 
-  Result<void> build(const PutDesc* descs, uint32_t n, int device);
+  // warm: as fused_put's; captured with the step
+  Result<void> build(const PutDesc* descs, uint32_t n, int device,
+                     WarmTail warm = {});
   bool ready() const { return impl_ != nullptr; }
   uint32_t size() const { return n_; }
   Result<void> run(uint64_t* out_digests);
