@@ -793,7 +793,7 @@ std::optional<std::vector<int32_t>> Client::try_host_session_put(
     const std::vector<PutItem>& items, HostPutSession* sess) {
   if (!sess || sess->token == 0 || sess->owner != this || items.empty())
     return std::nullopt;
-  const uint32_t dpi = std::max<uint32_t>(sess->descs_per_item, 1);
+  const uint32_t dpi = std::max<uint32_t>(sess->dsts_per_item, 1);
   if (sess->srcs.size() != items.size() ||
       sess->dsts.size() != items.size() * dpi)
     return std::nullopt;
@@ -924,7 +924,7 @@ Result<std::vector<int32_t>> Client::batch_put_once_v2(
                                 digests.data(), digests.size()).ok();
   if (keep_session && committed) {
     sess->token = token;
-    sess->descs_per_item = dpi;
+    sess->dsts_per_item = dpi;
     sess->dsts = std::move(sess_dsts);
     sess->srcs.clear();
     sess->sizes.clear();

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <future>
 #include <map>
+#include <span>
 
 #include <hip/hip_runtime_api.h>
 
@@ -47,6 +48,73 @@ struct KeysMsg {
 bool aligned16(const void* a, const void* b = nullptr) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) &
           15) == 0;
+}
+
+// key_of(x) of every x in `range`, for the placement cache
+template <typename Range, typename KeyOf>
+PlacementCache::KeyList key_list(const Range& range, KeyOf key_of) {
+  PlacementCache::KeyList list;
+  list.reserve(std::size(range));
+  for (const auto& x : range) list.push_back(&key_of(x));
+  return list;
+}
+
+// a one-item batch's answer as the single call's
+Result<void> first_status(const Result<std::vector<int32_t>>& r,
+                          const ObjectKey& key) {
+  if (!r.ok()) return r.error();
+  if (r.value()[0] != 0)
+    return Error{static_cast<ErrorCode>(r.value()[0]), key};
+  return {};
+}
+
+bool any_striped(const std::vector<CopyPlacement>& copies) {
+  for (const auto& c : copies)
+    if (c.shards.size() > 1) return true;
+  return false;
+}
+
+using StripeRange = GpuClient::StripeRange;
+using ShardDigests = std::vector<std::vector<uint64_t>>;
+
+// where item i's segments end in a list of nsegs
+size_t seg_end(const std::vector<StripeRange>& ranges, size_t i, size_t nsegs) {
+  return i + 1 < ranges.size() ? ranges[i + 1].first_seg : nsegs;
+}
+
+// every copy's object digest equals copy 0's
+bool copies_agree(const std::vector<uint64_t>& obj_digests,
+                  const StripeRange& r) {
+  for (uint32_t c = 1; c < r.ncopies; ++c)
+    if (obj_digests[r.first_obj + c] != obj_digests[r.first_obj]) return false;
+  return true;
+}
+
+// An item's flat segment digests regrouped per copy, for the wire. Either
+// from the copies themselves: copy c owns the next copies[c].shards.size()
+// digests from r.first_seg on…
+ShardDigests shard_digests_of(const StripeRange& r,
+                              const std::vector<CopyPlacement>& copies,
+                              const std::vector<uint64_t>& seg_digests) {
+  ShardDigests out;
+  out.reserve(copies.size());
+  auto at = seg_digests.begin() + r.first_seg;
+  for (const auto& c : copies) {
+    out.emplace_back(at, at + c.shards.size());
+    at += c.shards.size();
+  }
+  return out;
+}
+// …or from the launch's segment list: segs[k] of [r.first_seg, end) belongs
+// to copy segs[k].obj - r.first_obj.
+ShardDigests shard_digests_of(const StripeRange& r,
+                              const std::vector<gpu::StripeSeg>& segs,
+                              size_t end,
+                              const std::vector<uint64_t>& seg_digests) {
+  ShardDigests out(r.ncopies);
+  for (size_t k = r.first_seg; k < end; ++k)
+    out[segs[k].obj - r.first_obj].push_back(seg_digests[k]);
+  return out;
 }
 }  // namespace
 
@@ -594,12 +662,8 @@ Result<void> GpuClient::staged_read_many(
 
 Result<void> GpuClient::put_device(const ObjectKey& key, const void* dev_ptr,
                                    uint64_t size, const PlacementConfig& cfg) {
-  DevPutItem item{key, dev_ptr, size};
-  auto r = batch_put_device({item}, cfg);
-  if (!r.ok()) return r.error();
-  if (r.value()[0] != 0)
-    return Error{static_cast<ErrorCode>(r.value()[0]), key};
-  return {};
+  return first_status(batch_put_device({DevPutItem{key, dev_ptr, size}}, cfg),
+                      key);
 }
 
 Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
@@ -710,11 +774,8 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_range(
 
 Result<void> GpuClient::get_device_range(const ObjectKey& key, uint64_t offset,
                                          void* dev_ptr, uint64_t length) {
-  auto r = batch_get_device_range({DevRangeGet{key, offset, dev_ptr, length}});
-  if (!r.ok()) return r.error();
-  if (r.value()[0] != 0)
-    return Error{static_cast<ErrorCode>(r.value()[0]), key};
-  return {};
+  return first_status(
+      batch_get_device_range({DevRangeGet{key, offset, dev_ptr, length}}), key);
 }
 
 Result<void> GpuClient::patch_by_rewrite(const DevRangePatch& item,
@@ -756,22 +817,15 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
   if (!started.ok()) return started.error();
   // the patched keys leave the cache whatever becomes of them; this also
   // unbinds every session
-  {
-    PlacementCache::KeyList list;
-    for (const auto& k : keys) list.push_back(&k);
-    cache_.erase(list);
-  }
+  cache_.erase(key_list(
+      keys, [](const ObjectKey& k) -> const ObjectKey& { return k; }));
 
   // the one fused_patch launch: every copy of an item is a kernel object of
-  // its own, so diverged replicas show as different digests
-  struct Fused {
-    uint32_t item;
-    uint32_t first_obj, ncopies;
-    uint32_t first_shard;  // shards of copy 0, copy 1, … back to back
-  };
+  // its own, so diverged replicas show as different digests. An item's range
+  // counts shards (the digest lists), not the patched pieces.
   std::vector<gpu::PatchSeg> segs;
   std::vector<uint64_t> shard_lens, shard_old, obj_sizes, obj_old;
-  std::vector<Fused> fused;
+  std::vector<StripeRange> fused;
   std::vector<uint32_t> rewrite;  // item indices
   std::vector<GetWorkersResponse> rewrite_info(items.size());
   std::vector<ObjectKey> aborts;
@@ -868,22 +922,14 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
         cancels.push_back(key);
         continue;
       }
-      bool agree = true;
-      for (uint32_t c = 1; c < f.ncopies; ++c)
-        if (obj_new[f.first_obj + c] != obj_new[f.first_obj]) agree = false;
-      if (!agree) {
+      if (!copies_agree(obj_new, f)) {
         statuses[f.item] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
         cancels.push_back(key);
         continue;
       }
-      PutCompleteRequest pc{key, obj_new[f.first_obj], {}};
-      uint32_t at = f.first_shard;
-      for (const auto& copy : started->items[f.item].info.copies) {
-        pc.shard_digests.emplace_back(shard_new.begin() + at,
-                                      shard_new.begin() + at + copy.shards.size());
-        at += static_cast<uint32_t>(copy.shards.size());
-      }
-      reqs.push_back(std::move(pc));
+      reqs.push_back(PutCompleteRequest{
+          key, obj_new[f.first_obj],
+          shard_digests_of(f, started->items[f.item].info.copies, shard_new)});
       order.push_back(f.item);
     }
     c_.cancel_puts(cancels);
@@ -904,150 +950,107 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
 
 Result<void> GpuClient::patch_device(const ObjectKey& key, uint64_t offset,
                                      const void* dev_ptr, uint64_t length) {
-  auto r = batch_patch_device({DevRangePatch{key, offset, dev_ptr, length}});
-  if (!r.ok()) return r.error();
-  if (r.value()[0] != 0)
-    return Error{static_cast<ErrorCode>(r.value()[0]), key};
-  return {};
+  return first_status(
+      batch_patch_device({DevRangePatch{key, offset, dev_ptr, length}}), key);
 }
-
 
 // ------------------------ compact v2 batch protocol ------------------------
 // Pool-table responses with fixed-width placements: the client resolves each
 // POOL once (not each object) and decodes with zero per-item allocations.
 
-Result<void> GpuClient::session_kernel(SessionCore& sess, uint64_t* digests,
-                                       bool put) {
+// The launch of one session step, put or get, plain or striped.
+Result<GpuClient::StepDigests> GpuClient::session_step(SessionCore& sess,
+                                                       bool put) {
   static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
-  if (!no_graph && !sess.plan && !sess.plan_failed) {
-    auto plan = std::make_shared<gpu::FusedPutPlan>();
-    auto rb = plan->build(sess.descs.data(),
-                          static_cast<uint32_t>(sess.descs.size()), device_,
-                          warm_tail(put));
-    if (rb.ok()) {
-      sess.plan = std::move(plan);
-    } else {
-      sess.plan_failed = true;  // capture unsupported: launch path
-      (void)hipGetLastError();   // clear any sticky launch error
-      BB_LOG(WARN) << "session graph capture unavailable ("
-                   << rb.error().message << "); using per-op launches";
-    }
-  }
-  if (sess.plan) {
-    auto r = sess.plan->run(digests);
-    if (r.ok()) {
-      session_graph_steps_.fetch_add(1);
-      return r;
-    }
-    sess.plan.reset();  // replay failed: fall through to launches
-    sess.plan_failed = true;
-  }
-  return gpu::fused_put(sess.descs.data(),
-                        static_cast<uint32_t>(sess.descs.size()), digests,
-                        streams_[2], warm_tail(put));
-}
-
-Result<void> GpuClient::session_stripe_kernel(SessionCore& sess,
-                                              uint64_t* seg_digests,
-                                              uint64_t* obj_digests) {
-  static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
-  const uint32_t nseg = static_cast<uint32_t>(sess.segs.size());
-  const uint32_t nobj = static_cast<uint32_t>(sess.obj_sizes.size());
-  if (!no_graph && !sess.stripe_plan && !sess.plan_failed) {
-    auto plan = std::make_shared<gpu::FusedStripePlan>();
-    auto rb = plan->build(sess.segs.data(), nseg, sess.obj_sizes.data(), nobj,
-                          device_);
-    if (rb.ok()) {
-      sess.stripe_plan = std::move(plan);
-    } else {
-      sess.plan_failed = true;  // capture unsupported: launch path
-      (void)hipGetLastError();   // clear any sticky launch error
-      BB_LOG(WARN) << "striped session graph capture unavailable ("
-                   << rb.error().message << "); using per-op launches";
-    }
-  }
-  if (sess.stripe_plan) {
-    auto r = sess.stripe_plan->run(seg_digests, obj_digests);
-    if (r.ok()) {
-      session_graph_steps_.fetch_add(1);
-      return r;
-    }
-    sess.stripe_plan.reset();  // replay failed: fall through to launches
-    sess.plan_failed = true;
-  }
-  return gpu::fused_stripe(sess.segs.data(), nseg, sess.obj_sizes.data(), nobj,
-                           seg_digests, obj_digests, streams_[2]);
-}
-
-// Token fast path: placements unchanged since last step ⇒ two tiny RPCs
-// bracket ONE fused copy+digest kernel launch. Returns nullopt when the
-// session is not usable (caller runs the full path, which re-establishes it).
-std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
-    const std::vector<DevPutItem>& items, BatchPutSession* sess) {
-  if (sess && sess->striped()) return std::nullopt;  // the v1 path's session
-  const uint32_t dpi = sess ? std::max<uint32_t>(sess->descs_per_item, 1) : 1;
-  if (!sess || sess->token == 0 || !cache_.owns(sess->binding) ||
-      items.empty() || sess->descs.size() != items.size() * dpi)
-    return std::nullopt;
-  if (!cache_.valid(sess->binding)) {
-    sess->token = 0;
-    return std::nullopt;
-  }
-  // the session is bound to one item list: same buffers, same order
-  // (dpi descs per item for replicated sessions — same src, one dst/copy)
-  for (size_t i = 0; i < items.size(); ++i)
-    for (uint32_t k = 0; k < dpi; ++k)
-      if (sess->descs[i * dpi + k].src != items[i].ptr ||
-          sess->descs[i * dpi + k].nbytes != items[i].size) {
-        sess->token = 0;
-        return std::nullopt;
+  // the ladder of either form: build the plan lazily, replay it, launch
+  auto run = [&](auto& plan, auto build, auto replay,
+                 auto launch) -> Result<void> {
+    using Plan = typename std::decay_t<decltype(plan)>::element_type;
+    if (!no_graph && !plan && !sess.plan_failed) {
+      auto built = std::make_shared<Plan>();
+      auto rb = build(*built);
+      if (rb.ok()) {
+        plan = std::move(built);
+      } else {
+        sess.plan_failed = true;  // capture unsupported: launch path
+        (void)hipGetLastError();   // clear any sticky launch error
+        BB_LOG(WARN) << (sess.striped() ? "striped " : "")
+                     << "session graph capture unavailable ("
+                     << rb.error().message << "); using per-op launches";
       }
-  BB_TRACE_SCOPE("bb::session_put");
-  // RPC 1 (8 bytes): flip the session's objects to PENDING — placements are
-  // now pinned (tiering/eviction/repair only touch COMMITTED objects), so
-  // the one-sided writes below cannot race a migration
-  auto r1 = c_.meta_call_raw(M::BATCH_UPSERT_START,
-                             wire::encode_upsert_start(sess->token));
-  if (!r1.ok()) {
-    sess->token = 0;  // stale/error before any write: clean fallback
-    return std::nullopt;
+    }
+    if (plan) {
+      auto r = replay(*plan);
+      if (r.ok()) {
+        session_graph_steps_.fetch_add(1);
+        return r;
+      }
+      plan.reset();  // replay failed: fall through to launches
+      sess.plan_failed = true;
+    }
+    return launch();
+  };
+  StepDigests d;
+  Result<void> r{};
+  if (sess.striped()) {
+    const gpu::StripeSeg* segs = sess.segs.data();
+    const uint64_t* sizes = sess.obj_sizes.data();
+    const uint32_t nseg = static_cast<uint32_t>(sess.segs.size());
+    const uint32_t nobj = static_cast<uint32_t>(sess.obj_sizes.size());
+    d.seg.assign(nseg, 0);
+    d.obj.assign(nobj, 0);
+    r = run(
+        sess.stripe_plan,
+        [&](auto& p) { return p.build(segs, nseg, sizes, nobj, device_); },
+        [&](auto& p) { return p.run(d.seg.data(), d.obj.data()); },
+        [&] {
+          return gpu::fused_stripe(segs, nseg, sizes, nobj, d.seg.data(),
+                                   d.obj.data(), streams_[2]);
+        });
+  } else {
+    const gpu::PutDesc* descs = sess.descs.data();
+    const uint32_t n = static_cast<uint32_t>(sess.descs.size());
+    d.obj.assign(n, 0);
+    r = run(
+        sess.plan,
+        [&](auto& p) { return p.build(descs, n, device_, warm_tail(put)); },
+        [&](auto& p) { return p.run(d.obj.data()); },
+        [&] {
+          return gpu::fused_put(descs, n, d.obj.data(), streams_[2],
+                                warm_tail(put));
+        });
   }
-  std::vector<uint64_t> digests(sess->descs.size(), 0);
-  auto rk = session_kernel(*sess, digests.data(), /*put=*/true);
-  if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
-  // keep the session for the next step; one digest per ITEM (replicas hash
-  // identical bytes; take copy 0's)
-  auto r2 = c_.commit_by_token(sess->token, /*release=*/false, digests.data(),
-                               items.size(), dpi);
-  if (!r2.ok()) {
-    // placements changed mid-step (rare): fall back — the full path
-    // re-places and rewrites the batch
-    sess->token = 0;
-    return std::nullopt;
-  }
-  // refresh the cached digests so the verified get path accepts the new
-  // contents (a binding that went stale meanwhile is simply not refreshed)
-  (void)cache_.refresh_digests(sess->binding, digests.data(), dpi);
-  session_put_steps_.fetch_add(1);
-  return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
+  if (!r.ok()) return r.error();
+  return d;
 }
 
-// A striped session's segments still describe `items`: item i owns the
-// segments from its range to the next one's, each a slice of the item's
-// buffer (user_of(seg) == ptr + first_tile tiles) of an object whose size
-// fits size_ok(i, size).
-template <typename Item, typename UserOf, typename SizeOk>
-static bool stripe_session_matches(const GpuClient::SessionCore& s,
-                                   const std::vector<Item>& items,
-                                   UserOf user_of, SizeOk size_ok) {
+// A session's lists still describe `items`: item i owns the segments from
+// its range to the next one's, each a slice of the item's buffer (the user
+// side of the segment == ptr + first_tile tiles) of an object whose size
+// fits size_ok(i, size). A plain desc is a segment at tile 0 of its own
+// object: every copy of item i moves the whole buffer.
+template <bool Put, typename Item, typename SizeOk>
+static bool session_matches(const GpuClient::SessionCore& s,
+                            const std::vector<Item>& items, SizeOk size_ok) {
   if (s.ranges.size() != items.size()) return false;
+  auto user_of = [](const auto& seg) -> const void* {
+    if constexpr (Put) return seg.src;
+    else return seg.dst;
+  };
+  const bool striped = s.striped();
   for (size_t i = 0; i < items.size(); ++i) {
     const auto& r = s.ranges[i];
-    const size_t seg_end =
-        i + 1 < items.size() ? s.ranges[i + 1].first_seg : s.segs.size();
+    if (!striped) {
+      for (uint32_t k = r.first_seg; k < r.first_seg + r.ncopies; ++k)
+        if (user_of(s.descs[k]) != items[i].ptr ||
+            !size_ok(i, s.descs[k].nbytes))
+          return false;
+      continue;
+    }
     for (uint32_t c = 0; c < r.ncopies; ++c)
       if (!size_ok(i, s.obj_sizes[r.first_obj + c])) return false;
-    for (size_t k = r.first_seg; k < seg_end; ++k) {
+    for (size_t k = r.first_seg, end = seg_end(s.ranges, i, s.segs.size());
+         k < end; ++k) {
       const gpu::StripeSeg& seg = s.segs[k];
       if (seg.obj < r.first_obj || seg.obj >= r.first_obj + r.ncopies ||
           user_of(seg) != static_cast<const uint8_t*>(items[i].ptr) +
@@ -1058,89 +1061,121 @@ static bool stripe_session_matches(const GpuClient::SessionCore& s,
   return true;
 }
 
-// The striped put step: the same two RPCs around one FusedStripePlan replay;
-// the commit carries the object digests and every shard's own.
-std::optional<Result<std::vector<int32_t>>> GpuClient::try_striped_session_put(
-    const std::vector<DevPutItem>& items, BatchPutSession* sess) {
-  if (!sess || !sess->striped() || sess->token == 0 ||
+// Token fast path: placements unchanged since last step ⇒ two tiny RPCs
+// bracket ONE launch (session_step). Returns nullopt when the session is not
+// usable (caller runs the full path, which re-establishes it).
+std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_put(
+    const std::vector<DevPutItem>& items, BatchPutSession* sess,
+    bool striped_route) {
+  if (!sess || sess->striped() != striped_route || sess->token == 0 ||
       !cache_.owns(sess->binding) || items.empty())
     return std::nullopt;
+  // the session is bound to one item list: same buffers, same order
   if (!cache_.valid(sess->binding) ||
-      !stripe_session_matches(
-          *sess, items, [](const gpu::StripeSeg& s) { return s.src; },
-          [&](size_t i, uint64_t size) { return size == items[i].size; })) {
+      !session_matches<true>(*sess, items, [&](size_t i, uint64_t size) {
+        return size == items[i].size;
+      })) {
     sess->token = 0;
     return std::nullopt;
   }
-  BB_TRACE_SCOPE("bb::session_put_striped");
-  // PENDING pins the placements before the one-sided writes (see
-  // try_session_put)
+  BB_TRACE_SCOPE(striped_route ? "bb::session_put_striped"
+                               : "bb::session_put");
+  // RPC 1 (8 bytes): flip the session's objects to PENDING — placements are
+  // now pinned (tiering/eviction/repair only touch COMMITTED objects), so
+  // the one-sided writes below cannot race a migration
   auto r1 = c_.meta_call_raw(M::BATCH_UPSERT_START,
                              wire::encode_upsert_start(sess->token));
   if (!r1.ok()) {
     sess->token = 0;  // stale/error before any write: clean fallback
     return std::nullopt;
   }
-  std::vector<uint64_t> seg_digests(sess->segs.size(), 0);
-  std::vector<uint64_t> obj_digests(sess->obj_sizes.size(), 0);
-  auto rk = session_stripe_kernel(*sess, seg_digests.data(), obj_digests.data());
-  if (!rk.ok()) return {rk.error()};  // objects stay PENDING; GC reclaims
-  // one digest per ITEM: copy 0's. A replica that disagrees saw the source
-  // change mid-step and must not commit — as on the one-shot path its item
-  // fails and is cancelled; the others commit by key, and the session ends.
-  std::vector<uint64_t> digests(items.size());
+  auto step = session_step(*sess, /*put=*/true);
+  if (!step.ok()) return {step.error()};  // objects stay PENDING; GC reclaims
+  const StepDigests& d = step.value();
   std::vector<int32_t> statuses(items.size(), 0);
-  bool agree = true;
-  for (size_t i = 0; i < items.size(); ++i) {
-    const auto& r = sess->ranges[i];
-    digests[i] = obj_digests[r.first_obj];
-    for (uint32_t c = 1; c < r.ncopies; ++c)
-      if (obj_digests[r.first_obj + c] != digests[i]) {
+  // keep the session for the next step; one digest per ITEM, copy 0's, which
+  // the plain form reads in place, its copies a fixed stride apart
+  const uint64_t* digests = d.obj.data();
+  size_t stride = sess->ranges[0].ncopies;
+  std::vector<uint64_t> per_item;
+  Result<void> r2{};
+  if (!sess->striped()) {
+    // (replicas hash identical bytes; they are not compared here)
+    r2 = c_.commit_by_token(sess->token, /*release=*/false, digests,
+                            items.size(), static_cast<uint32_t>(stride));
+  } else {
+    // A replica that disagrees saw the source change mid-step and must not
+    // commit — as on the one-shot path its item fails and is cancelled; the
+    // others commit by key, and the session ends.
+    per_item.resize(items.size());
+    bool agree = true;
+    for (size_t i = 0; i < items.size(); ++i) {
+      const auto& r = sess->ranges[i];
+      per_item[i] = d.obj[r.first_obj];
+      if (!copies_agree(d.obj, r)) {
         statuses[i] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
         agree = false;
       }
-  }
-  if (!agree) {
-    sess->token = 0;
-    std::vector<PutCompleteRequest> reqs;
-    std::vector<uint32_t> order;
-    for (size_t i = 0; i < items.size(); ++i) {
-      if (statuses[i] != 0) continue;
-      const auto& r = sess->ranges[i];
-      const size_t seg_end =
-          i + 1 < items.size() ? sess->ranges[i + 1].first_seg : sess->segs.size();
-      PutCompleteRequest pc{items[i].key, digests[i], {}};
-      pc.shard_digests.resize(r.ncopies);
-      for (size_t k = r.first_seg; k < seg_end; ++k)
-        pc.shard_digests[sess->segs[k].obj - r.first_obj].push_back(
-            seg_digests[k]);
-      reqs.push_back(std::move(pc));
-      order.push_back(static_cast<uint32_t>(i));
     }
-    if (auto r = c_.complete_by_keys(reqs, order, &statuses); !r.ok())
-      return {r.error()};
-    cancel_failed(items, statuses);
-    return {Result<std::vector<int32_t>>(std::move(statuses))};
+    if (!agree) {
+      sess->token = 0;
+      std::vector<PutCompleteRequest> reqs;
+      std::vector<uint32_t> order;
+      for (size_t i = 0; i < items.size(); ++i) {
+        if (statuses[i] != 0) continue;
+        reqs.push_back(PutCompleteRequest{
+            items[i].key, per_item[i],
+            shard_digests_of(sess->ranges[i], sess->segs,
+                             seg_end(sess->ranges, i, sess->segs.size()),
+                             d.seg)});
+        order.push_back(static_cast<uint32_t>(i));
+      }
+      if (auto r = c_.complete_by_keys(reqs, order, &statuses); !r.ok())
+        return {r.error()};
+      cancel_failed(items, statuses);
+      return {Result<std::vector<int32_t>>(std::move(statuses))};
+    }
+    digests = per_item.data();
+    stride = 1;
+    // segments lie in item, copy, shard order: the wire order of the digests
+    r2 = c_.commit_by_token_shards(sess->token, /*release=*/false, digests,
+                                   items.size(), d.seg.data(), d.seg.size());
   }
-  // segments lie in item, copy, shard order: the wire order of the digests
-  auto r2 = c_.commit_by_token_shards(sess->token, /*release=*/false,
-                                      digests.data(), digests.size(),
-                                      seg_digests.data(), seg_digests.size());
   if (!r2.ok()) {
-    // placements changed mid-step (rare): the full path re-places and
-    // rewrites the batch
+    // placements changed mid-step (rare): fall back — the full path
+    // re-places and rewrites the batch
     sess->token = 0;
     return std::nullopt;
   }
-  (void)cache_.refresh_digests(sess->binding, digests.data());
+  // refresh the cached digests so the verified get path accepts the new
+  // contents (a binding that went stale meanwhile is simply not refreshed)
+  (void)cache_.refresh_digests(sess->binding, digests, stride);
   session_put_steps_.fetch_add(1);
   return {Result<std::vector<int32_t>>(std::move(statuses))};
+}
+
+// What both put paths do with the placements they transferred.
+template <typename Rebind>
+void GpuClient::record_puts(const std::vector<PlacementCache::Put>& cached,
+                            bool bind, uint64_t token, BatchPutSession* sess,
+                            Rebind rebind) {
+  PlacementCache::KeyList keys;
+  if (bind)
+    keys = key_list(cached, [](const PlacementCache::Put& p) -> const ObjectKey& {
+      return p.key;
+    });
+  auto binding = cache_.record(cached, bind ? &keys : nullptr);
+  if (!bind) return;
+  sess->token = binding.bound() ? token : 0;
+  if (binding.bound()) rebind(std::move(binding));
+  else sess->rebind({}, 1, {});
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
     const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
     BatchPutSession* sess) {
-  if (auto fast = try_session_put(items, sess)) return std::move(*fast);
+  if (auto fast = try_session_put(items, sess, /*striped_route=*/false))
+    return std::move(*fast);
   BB_TRACE_SCOPE("bb::batch_put");
   // establish: a reusable session for upsert steps (token kept server-side;
   // replicated single-shard placements qualify — one desc per copy)
@@ -1238,16 +1273,9 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
     // item rode the fused single-copy path (so desc j == item j) AND every
     // key is cached after recording
     const bool bind = sess && establish && token != 0 && all_hashed;
-    PlacementCache::KeyList keys;
-    if (bind)
-      for (const auto& p : cached) keys.push_back(&p.key);
-    auto binding = cache_.record(cached, bind ? &keys : nullptr);
-    if (bind) {
-      sess->descs_per_item = dpi;
-      sess->token = binding.bound() ? token : 0;
-      if (binding.bound()) sess->rebind(rt.hashed, std::move(binding));
-      else sess->rebind({}, {});
-    }
+    record_puts(cached, bind, token, sess, [&](PlacementCache::Binding b) {
+      sess->rebind(rt.hashed, dpi, std::move(b));
+    });
   }
   cancel_failed(items, statuses);
   return statuses;
@@ -1256,9 +1284,8 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_v2(
 // ----------------------------------------------- verified placement cache
 
 void GpuClient::invalidate(const std::vector<ObjectKey>& keys) {
-  PlacementCache::KeyList list;
-  for (const auto& k : keys) list.push_back(&k);
-  cache_.erase(list);
+  cache_.erase(key_list(
+      keys, [](const ObjectKey& k) -> const ObjectKey& { return k; }));
 }
 
 Result<void> GpuClient::refetch(const std::vector<DevGetItem>& items,
@@ -1277,84 +1304,43 @@ Result<void> GpuClient::refetch(const std::vector<DevGetItem>& items,
 // previous step; a step is ONE kernel launch + digest compares, zero RPCs.
 std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_get(
     const std::vector<DevGetItem>& items, BatchGetSession* sess) {
-  if (sess && sess->striped()) return try_striped_session_get(items, sess);
-  if (!sess || !sess->complete || !cache_.owns(sess->binding) ||
-      sess->descs.size() != items.size() || items.empty())
+  if (!sess || !sess->complete || !cache_.owns(sess->binding) || items.empty())
     return std::nullopt;
   std::vector<uint64_t> want(items.size());
-  if (!cache_.read_digests(sess->binding, want.data(), want.size())) {
+  if (!cache_.read_digests(sess->binding, want.data(), want.size()) ||
+      !session_matches<false>(*sess, items, [&](size_t i, uint64_t size) {
+        return size <= items[i].capacity;
+      })) {
     sess->complete = false;
     return std::nullopt;
   }
-  for (size_t i = 0; i < items.size(); ++i)
-    if (sess->descs[i].dst != items[i].ptr ||
-        sess->descs[i].nbytes > items[i].capacity) {
-      sess->complete = false;
-      return std::nullopt;
-    }
-  BB_TRACE_SCOPE("bb::session_get");
-  std::vector<uint64_t> got(items.size(), 0);
-  auto rk = session_kernel(*sess, got.data(), /*put=*/false);
-  if (!rk.ok()) return {rk.error()};
-  std::vector<uint32_t> miss;
-  for (size_t j = 0; j < items.size(); ++j)
-    if (got[j] != want[j]) miss.push_back(static_cast<uint32_t>(j));
-  if (miss.empty()) {
-    session_get_steps_.fetch_add(1);
-    return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
-  }
-  // stale entries: drop them (which ends every session on this cache) and
-  // refetch the misses authoritatively
-  PlacementCache::KeyList stale;
-  for (auto j : miss) stale.push_back(&items[j].key);
-  cache_.erase(stale);
-  sess->complete = false;
-  std::vector<int32_t> statuses(items.size(), 0);
-  if (auto r = refetch(items, miss, /*verify=*/true, statuses); !r.ok())
-    return {r.error()};
-  return {Result<std::vector<int32_t>>(std::move(statuses))};
-}
-
-// The striped get step: one FusedStripePlan replay gathers every shard into
-// the user buffers; the object digests are compared with the cached ones.
-std::optional<Result<std::vector<int32_t>>> GpuClient::try_striped_session_get(
-    const std::vector<DevGetItem>& items, BatchGetSession* sess) {
-  if (!sess->complete || !cache_.owns(sess->binding) || items.empty())
-    return std::nullopt;
-  std::vector<uint64_t> want(items.size());
-  if (sess->ranges.size() != items.size() ||
-      !cache_.read_digests(sess->binding, want.data(), want.size()) ||
-      !stripe_session_matches(
-          *sess, items,
-          [](const gpu::StripeSeg& s) {
-            return static_cast<const void*>(s.dst);
-          },
-          [&](size_t i, uint64_t size) { return size <= items[i].capacity; })) {
-    sess->complete = false;
-    return std::nullopt;
-  }
-  BB_TRACE_SCOPE("bb::session_get_striped");
-  std::vector<uint64_t> seg_got(sess->segs.size(), 0);
-  std::vector<uint64_t> got(sess->obj_sizes.size(), 0);
-  auto rk = session_stripe_kernel(*sess, seg_got.data(), got.data());
-  if (!rk.ok()) return {rk.error()};
+  BB_TRACE_SCOPE(sess->striped() ? "bb::session_get_striped"
+                                 : "bb::session_get");
+  auto step = session_step(*sess, /*put=*/false);
+  if (!step.ok()) return {step.error()};
+  // copy 0's object digest of every item against the cached one
+  const std::vector<uint64_t>& got = step.value().obj;
   std::vector<uint32_t> miss;
   for (size_t j = 0; j < items.size(); ++j)
     if (got[sess->ranges[j].first_obj] != want[j])
       miss.push_back(static_cast<uint32_t>(j));
-  if (miss.empty()) {
-    session_get_steps_.fetch_add(1);
-    return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
-  }
-  // stale entries: as in try_session_get
-  PlacementCache::KeyList stale;
-  for (auto j : miss) stale.push_back(&items[j].key);
-  cache_.erase(stale);
-  sess->complete = false;
+  if (!miss.empty()) return {refetch_stale(items, miss, *sess)};
+  session_get_steps_.fetch_add(1);
+  return {Result<std::vector<int32_t>>(std::vector<int32_t>(items.size(), 0))};
+}
+
+// Stale entries: drop them (which ends every session on this cache) and
+// refetch the misses authoritatively.
+Result<std::vector<int32_t>> GpuClient::refetch_stale(
+    const std::vector<DevGetItem>& items, const std::vector<uint32_t>& miss,
+    BatchGetSession& sess) {
+  cache_.erase(key_list(miss, [&](uint32_t j) -> const ObjectKey& {
+    return items[j].key;
+  }));
+  sess.complete = false;
   std::vector<int32_t> statuses(items.size(), 0);
-  if (auto r = refetch(items, miss, /*verify=*/true, statuses); !r.ok())
-    return {r.error()};
-  return {Result<std::vector<int32_t>>(std::move(statuses))};
+  BB_RETURN_IF_ERROR(refetch(items, miss, /*verify=*/true, statuses));
+  return statuses;
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
@@ -1409,17 +1395,17 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
     if (!r.ok()) return r.error();
     BB_RETURN_IF_ERROR(stripes.run(streams_[2]));
     striped_fused_get_items_.fetch_add(stripes.entries.size());
-    PlacementCache::KeyList stale;
+    // digest mismatches join the misses (refetched authoritatively); their
+    // keys are the stale ones
+    const size_t first_stale = miss_idx.size();
     for (size_t j = 0; j < hit_idx.size(); ++j)
-      if (got[j] != want[j]) {
-        stale.push_back(&items[hit_idx[j]].key);
-        miss_idx.push_back(hit_idx[j]);  // refetch authoritatively
-      }
+      if (got[j] != want[j]) miss_idx.push_back(hit_idx[j]);
     for (size_t j = 0; j < stripes.entries.size(); ++j)
-      if (stripes.obj_digests[stripes.entries[j].first_obj] != stripe_want[j]) {
-        stale.push_back(&items[stripes.entries[j].item].key);
+      if (stripes.obj_digests[stripes.entries[j].first_obj] != stripe_want[j])
         miss_idx.push_back(stripes.entries[j].item);
-      }
+    const auto stale = key_list(
+        std::span<const uint32_t>(miss_idx).subspan(first_stale),
+        [&](uint32_t i) -> const ObjectKey& { return items[i].key; });
     // establish the get session when every item was a verified cache hit of
     // ONE kind (desc j == item j, or striped range j == item j; a mixed
     // batch gets none) and no concurrent thread mutated the cache
@@ -1433,7 +1419,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_v2(
                              std::move(stripes.obj_sizes),
                              std::move(stripes.entries), std::move(binding));
       else
-        sess->rebind(std::move(descs), std::move(binding));
+        sess->rebind(std::move(descs), /*copies=*/1, std::move(binding));
       sess->complete = true;
     }
   }
@@ -1530,7 +1516,8 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
   if (cfg.max_workers_per_copy <= 1)
     return batch_put_device_v2(items, cfg, sess);
 
-  if (auto fast = try_striped_session_put(items, sess)) return std::move(*fast);
+  if (auto fast = try_session_put(items, sess, /*striped_route=*/true))
+    return std::move(*fast);
   BatchPutStartRequest breq;
   breq.requests.reserve(items.size());
   for (const auto& it : items)
@@ -1564,12 +1551,9 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
     // tile boundary of the object → the item rides the fused_stripe launch
     // (copy, per-shard digests and object digest from one read)
     if (fused_copy_ && cfg.checksum && aligned16(items[i].ptr)) {
-      bool striped = false;
-      for (const auto& copy : placed.copies)
-        if (copy.shards.size() > 1) striped = true;
       const size_t seg_mark = stripes.segs.size();
       const size_t obj_mark = stripes.obj_sizes.size();
-      bool all = striped;
+      bool all = any_striped(placed.copies);
       for (size_t c = 0; c < placed.copies.size() && all; ++c)
         all = stripes.add_copy<true>(*this,
                                      static_cast<const uint8_t*>(items[i].ptr),
@@ -1608,10 +1592,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
     std::vector<uint32_t> slot_idx;
     for (auto i : rt.plain_idx) {
       const auto& copies = start->items[i].copies;
-      bool striped = false;
-      for (const auto& c : copies)
-        if (c.shards.size() > 1) striped = true;
-      if (!striped) continue;
+      if (!any_striped(copies)) continue;
       auto& out = shard_digests[i];
       out.resize(copies.size());
       for (uint32_t c = 0; c < copies.size(); ++c) {
@@ -1640,19 +1621,12 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
   // change mid-batch and must not commit), the shard digests are the
   // launch's segment digests in copy, shard order
   for (const auto& e : stripes.entries) {
-    const auto& copies = start->items[e.item].copies;
-    const uint64_t digest = stripes.obj_digests[e.first_obj];
-    for (uint32_t c = 1; c < e.ncopies; ++c)
-      if (stripes.obj_digests[e.first_obj + c] != digest)
-        statuses[e.item] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
-    auto& out = shard_digests[e.item];
-    out.resize(copies.size());
-    size_t k = e.first_seg;
-    for (uint32_t c = 0; c < copies.size(); ++c)
-      for (size_t s2 = 0; s2 < copies[c].shards.size(); ++s2)
-        out[c].push_back(stripes.seg_digests[k++]);
+    if (!copies_agree(stripes.obj_digests, e))
+      statuses[e.item] = static_cast<int32_t>(ErrorCode::TRANSFER_FAILED);
+    shard_digests[e.item] = shard_digests_of(e, start->items[e.item].copies,
+                                             stripes.seg_digests);
     rt.plain_idx.push_back(e.item);
-    rt.plain_digests.push_back(digest);
+    rt.plain_digests.push_back(stripes.obj_digests[e.first_obj]);
   }
   striped_fused_items_.fetch_add(stripes.entries.size());
 
@@ -1700,19 +1674,11 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
       cached.push_back({items[e.item].key, std::move(ce)});
     }
     const bool bind = committed_by_token && cached.size() == items.size();
-    PlacementCache::KeyList keys;
-    if (bind)
-      for (const auto& p : cached) keys.push_back(&p.key);
-    auto binding = cache_.record(cached, bind ? &keys : nullptr);
-    if (bind) {
-      sess->token = binding.bound() ? token : 0;
-      if (binding.bound())
-        sess->rebind_striped(std::move(stripes.segs),
-                             std::move(stripes.obj_sizes),
-                             std::move(stripes.entries), std::move(binding));
-      else
-        sess->rebind({}, {});
-    }
+    record_puts(cached, bind, token, sess, [&](PlacementCache::Binding b) {
+      sess->rebind_striped(std::move(stripes.segs),
+                           std::move(stripes.obj_sizes),
+                           std::move(stripes.entries), std::move(b));
+    });
   }
   cancel_failed(items, statuses);
   return statuses;
@@ -1833,30 +1799,30 @@ Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
 
 // ------------------------------------------------------- pipelined batches
 
-Result<uint64_t> GpuClient::batch_put_async(std::vector<DevPutItem> items,
-                                            PlacementConfig cfg) {
+template <typename Fn>
+Result<uint64_t> GpuClient::submit_async(Fn fn) {
   if (!initialized_) BB_RETURN_IF_ERROR(init());
   std::lock_guard<std::mutex> g(async_mu_);
   uint64_t token = next_async_++;
-  async_[token] = std::async(
-      std::launch::async, [this, items = std::move(items), cfg] {
-        (void)hipSetDevice(device_);
-        return batch_put_device(items, cfg);
-      });
+  async_[token] = std::async(std::launch::async, [this, fn = std::move(fn)] {
+    (void)hipSetDevice(device_);
+    return fn();
+  });
   return token;
+}
+
+Result<uint64_t> GpuClient::batch_put_async(std::vector<DevPutItem> items,
+                                            PlacementConfig cfg) {
+  return submit_async([this, items = std::move(items), cfg] {
+    return batch_put_device(items, cfg);
+  });
 }
 
 Result<uint64_t> GpuClient::batch_get_async(std::vector<DevGetItem> items,
                                             bool verify) {
-  if (!initialized_) BB_RETURN_IF_ERROR(init());
-  std::lock_guard<std::mutex> g(async_mu_);
-  uint64_t token = next_async_++;
-  async_[token] = std::async(
-      std::launch::async, [this, items = std::move(items), verify] {
-        (void)hipSetDevice(device_);
-        return batch_get_device(items, verify);
-      });
-  return token;
+  return submit_async([this, items = std::move(items), verify] {
+    return batch_get_device(items, verify);
+  });
 }
 
 Result<std::vector<int32_t>> GpuClient::async_wait(uint64_t token) {

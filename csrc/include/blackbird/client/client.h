@@ -109,8 +109,8 @@ class Client {
   // any server-side placement change invalidates it transparently.
   struct HostPutSession {
     uint64_t token = 0;
-    uint32_t descs_per_item = 1;       // one dst per copy
-    std::vector<uint8_t*> dsts;        // items.size() * descs_per_item
+    uint32_t dsts_per_item = 1;       // one dst per copy
+    std::vector<uint8_t*> dsts;        // items.size() * dsts_per_item
     std::vector<const void*> srcs;     // bound item buffers
     std::vector<uint64_t> sizes;
     void* owner = nullptr;

@@ -85,7 +85,9 @@ class GpuClient {
   // mismatch → RPC fallback; an EMBEDDED worker that frees its pool
   // in-process can fault — stop in-process workers only after their
   // clients.
-  // Where one item's kernel objects and segments sit in a striped launch.
+  // Where one item's kernel objects and segments sit in a launch: a striped
+  // one, a patch (first_seg then counts shards), or a plain session's desc
+  // list, where every desc is both an object and its only segment.
   struct StripeRange {
     uint32_t item;
     uint32_t first_obj, ncopies;  // kernel objects [first_obj, +ncopies)
@@ -93,24 +95,31 @@ class GpuClient {
   };
   struct SessionCore {
     PlacementCache::Binding binding;  // the items' digest slots, item order
-    std::vector<gpu::PutDesc> descs;  // user buffer ↔ pool range
-    // striped form (descs empty): the fused_stripe argument lists and each
-    // item's range into them, item order
+    // plain form: user buffer ↔ pool range, one desc PER COPY per item (same
+    // user buffer, one pool range per replica), item order
+    std::vector<gpu::PutDesc> descs;
+    // striped form (descs empty): the fused_stripe argument lists
     std::vector<gpu::StripeSeg> segs;
     std::vector<uint64_t> obj_sizes;
+    // both forms: item i's range into the lists above
     std::vector<StripeRange> ranges;
-    std::shared_ptr<gpu::FusedStripePlan> stripe_plan;  // lazily built too
     bool striped() const { return !segs.empty(); }
-    // hipGraph replay of the step (descs fixed ⇒ captured once, one graph
-    // launch per step); built lazily on the first session step
+    // hipGraph replay of the step (lists fixed ⇒ captured once, one graph
+    // launch per step), of the form the session holds; built lazily on the
+    // first session step
     std::shared_ptr<gpu::FusedPutPlan> plan;
-    bool plan_failed = false;  // capture unsupported: stay on fused_put
-    // a new desc list: a kept plan would replay the old one
-    void rebind(std::vector<gpu::PutDesc> d, PlacementCache::Binding b) {
+    std::shared_ptr<gpu::FusedStripePlan> stripe_plan;
+    bool plan_failed = false;  // capture unsupported: stay on launches
+    // a new desc list (`copies` descs per item): a kept plan would replay
+    // the old one
+    void rebind(std::vector<gpu::PutDesc> d, uint32_t copies,
+                PlacementCache::Binding b) {
       descs = std::move(d);
       segs.clear();
       obj_sizes.clear();
-      ranges.clear();
+      ranges.resize(descs.size() / copies);
+      for (uint32_t i = 0; i < ranges.size(); ++i)
+        ranges[i] = {i, i * copies, copies, i * copies};
       reset(std::move(b));
     }
     void rebind_striped(std::vector<gpu::StripeSeg> s,
@@ -133,9 +142,6 @@ class GpuClient {
   };
   struct BatchPutSession : SessionCore {  // descs: src=user, dst=pool
     uint64_t token = 0;  // server put-session token (0 = not established)
-    // replicated sessions carry one desc PER COPY per item (same src, one
-    // dst per replica); descs.size() == items.size() * descs_per_item
-    uint32_t descs_per_item = 1;
   };
   struct BatchGetSession : SessionCore {  // descs: src=pool, dst=user
     bool complete = false;  // covers every item
@@ -302,11 +308,25 @@ class GpuClient {
   Result<std::vector<int32_t>> batch_put_device_v2(
       const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
       BatchPutSession* sess);
-  // token fast path; returns statuses when taken, nullopt → run full path
+  // session fast paths; statuses when taken, nullopt → run the full path.
+  // `striped_route`: the caller is the striped put path; a session of the
+  // other form is left alone (the full path re-establishes it).
   std::optional<Result<std::vector<int32_t>>> try_session_put(
-      const std::vector<DevPutItem>& items, BatchPutSession* sess);
+      const std::vector<DevPutItem>& items, BatchPutSession* sess,
+      bool striped_route);
   std::optional<Result<std::vector<int32_t>>> try_session_get(
       const std::vector<DevGetItem>& items, BatchGetSession* sess);
+  // a get step's stale hits: their keys leave the cache (which ends every
+  // session on it), the get session ends, the items are refetched verified
+  Result<std::vector<int32_t>> refetch_stale(
+      const std::vector<DevGetItem>& items, const std::vector<uint32_t>& miss,
+      BatchGetSession& sess);
+  // what both put paths do with the placements they transferred: record
+  // them and, with `bind`, hand the binding to `rebind` — or end the
+  // session if the cache would not bind
+  template <typename Rebind>
+  void record_puts(const std::vector<PlacementCache::Put>& cached, bool bind,
+                   uint64_t token, BatchPutSession* sess, Rebind rebind);
   Result<std::vector<int32_t>> batch_get_device_v2(
       const std::vector<DevGetItem>& items, bool verify,
       BatchGetSession* sess);
@@ -363,24 +383,23 @@ class GpuClient {
   // the rewrite route of one patch item (info: what the keystone holds)
   Result<void> patch_by_rewrite(const DevRangePatch& item,
                                 const GetWorkersResponse& info);
-  // run the session desc list: captured-graph replay when available,
-  // fused_put launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1
-  // or a failed capture pins the session to the launch path)
-  Result<void> session_kernel(SessionCore& sess, uint64_t* digests, bool put);
+  // One session step's launch, whichever form the session holds: the replay
+  // of its captured graph when there is one, fused_put / fused_stripe
+  // launches otherwise (builds the plan lazily; BB_NO_HIPGRAPH=1 or a failed
+  // capture or replay pins the session to launches until it is rebound).
+  struct StepDigests {
+    std::vector<uint64_t> obj;  // one per kernel object (plain: per desc)
+    std::vector<uint64_t> seg;  // one per segment; empty for the plain form
+  };
+  Result<StepDigests> session_step(SessionCore& sess, bool put);
   // The warm tail a copy+digest launch of this client asks for, decided here
   // for every path: a put leaves its budget's worth of the batch on-die,
   // and a get loads the same tail plainly (nontemporal loads of resident
   // lines measured slower with two lanes, profiles/warm_tail_checks.md).
   gpu::WarmTail warm_tail(bool put) const { return {warm_tail_bytes_, !put}; }
-  // the same over a striped session's segment list (FusedStripePlan replay,
-  // fused_stripe launches otherwise)
-  Result<void> session_stripe_kernel(SessionCore& sess, uint64_t* seg_digests,
-                                     uint64_t* obj_digests);
-  // the striped forms of the two session steps
-  std::optional<Result<std::vector<int32_t>>> try_striped_session_put(
-      const std::vector<DevPutItem>& items, BatchPutSession* sess);
-  std::optional<Result<std::vector<int32_t>>> try_striped_session_get(
-      const std::vector<DevGetItem>& items, BatchGetSession* sess);
+  // the body of the two async entry points
+  template <typename Fn>
+  Result<uint64_t> submit_async(Fn fn);
   bool fused_copy_ = true;
   uint64_t warm_tail_bytes_ = kDefaultWarmTailBytes;
   bool initialized_ = false;
