@@ -33,20 +33,33 @@ struct BatchBlock {
   uint64_t* out(void* base) const { return prefix(base) + n; }
 };
 
+// Tiles that hold nbytes, the last one possibly in part: the digest's 1-KiB
+// tiles, or the work quantum of another kernel.
+inline uint64_t tile_count(uint64_t nbytes,
+                           uint64_t quantum = digest::kTileBytes) {
+  return (nbytes + quantum - 1) / quantum;
+}
+
+// The exclusive prefix sum of the tile counts of CopyDescs, StripeSegs or
+// PatchSegs, which the kernels' find_seg searches. Returns the total.
+template <typename Desc>
+uint64_t fill_prefix(const Desc* descs, uint32_t n, uint64_t quantum,
+                     uint64_t* prefix) {
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    prefix[i] = total;
+    total += tile_count(descs[i].nbytes, quantum);
+  }
+  return total;
+}
+
 // Copies the caller's descriptors into the host image (they may already be
-// there) and writes the exclusive prefix sum of their sizes in units of
-// `quantum` bytes. Returns the total number of quanta.
+// there) and writes their prefix sum. Returns the total number of quanta.
 inline uint64_t fill_block(const BatchBlock& b, void* host, const CopyDesc* descs,
                            uint64_t quantum) {
   CopyDesc* h_descs = b.descs(host);
-  uint64_t* h_prefix = b.prefix(host);
   if (descs != h_descs) std::memcpy(h_descs, descs, b.n * sizeof(CopyDesc));
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < b.n; ++i) {
-    h_prefix[i] = total;
-    total += (h_descs[i].nbytes + quantum - 1) / quantum;
-  }
-  return total;
+  return fill_prefix(h_descs, b.n, quantum, b.prefix(host));
 }
 
 // Two tiles per wave, capped at 4096 workgroups; the kernels split whatever

@@ -171,7 +171,7 @@ int digest_walk_depth() { return kWalkDepth; }
 Result<void> checksum_async(const void* dev_ptr, uint64_t nbytes, uint64_t* dev_out,
                             hipStream_t stream) {
   BB_HIP_TRY(hipMemsetAsync(dev_out, 0, sizeof(uint64_t), stream));
-  const uint64_t ntiles = (nbytes + kTileBytes - 1) / kTileBytes;
+  const uint64_t ntiles = tile_count(nbytes);
   if (ntiles > 0) {
     bbhash64_kernel<<<digest_grid(ntiles), kBlock, 0, stream>>>(
         static_cast<const uint8_t*>(dev_ptr), nbytes,

@@ -1,8 +1,11 @@
 // Device-side building blocks of the batched kernels: the bbhash64 tile
-// helpers, the prefix search, and the tile walk shared by the hash-only
-// kernel, the fused copy+digest kernel (digest.hip) and the striped
-// copy+digest kernel (stripe.hip); batched_copy in memops.hip uses the
-// search. Spec: csrc/include/blackbird/gpu/digest_spec.h.
+// helpers, the prefix search, and the tile walks. One range rule
+// (wave_tile_range), one boundary loop (walk_descs) and one pipelined run
+// (run_tiles) serve both: digest_walk (the hash-only and fused copy+digest
+// kernels of digest.hip, the striped one of stripe.hip) and patch_walk
+// (patch.hip) add what they do with a tile and with a descriptor's sums.
+// batched_copy in memops.hip uses the search.
+// Spec: csrc/include/blackbird/gpu/digest_spec.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -240,26 +243,158 @@ __device__ inline uint64_t hash_tile_frag(const i32x4& a_frag,
 // (profiles/walk_pipeline_checks.md).
 constexpr int kWalkDepth = 4;
 
-// Longest run of full tiles the walk takes in one go (1 TiB).
+// Longest run of full tiles a walk takes in one go (1 TiB).
 constexpr uint32_t kMaxRun = 1u << 30;
+
+// The range rule of every batched walk: each wave owns one CONTIGUOUS range
+// [begin, end) of the launch's global tiles, total_tiles split evenly over
+// the waves of the grid (sized by the host: digest_grid). False: none is left
+// for this wave. The wave index and all that follows from it are the same in
+// every lane, and the compiler is told so.
+__device__ inline bool wave_tile_range(uint64_t total_tiles, uint64_t& begin,
+                                       uint64_t& end) {
+  const uint32_t wave = wave_uniform(threadIdx.x >> 6);
+  const uint64_t gwave =
+      static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
+  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
+  const uint64_t per = (total_tiles + nwaves - 1) / nwaves;
+  begin = gwave * per;
+  end = begin + per < total_tiles ? begin + per : total_tiles;
+  return begin < total_tiles;
+}
+
+// The boundary loop of every batched walk. One desc = one contiguous run of
+// bytes that starts on a tile boundary; tile_prefix[i] is the global index of
+// desc i's first 1-KiB tile. The global tiles [begin, end), begin < end, are
+// cut into runs of full tiles of one desc plus at most one tail tile per
+// desc, so desc switches happen only at desc boundaries inside the range.
+// The current desc and its boundaries live in scalar registers (a per-tile
+// global load of descs[]/tile_prefix[] serializes on L2 latency). The walk
+// brings:
+//   enter(d)         desc d is the current one from here on; returns its
+//                    wave-uniform byte count
+//   leave(i)         the range holds no more of desc i: flush its sums
+//   full_run(t0, n)  n >= 1 full tiles of the current desc, from its tile t0
+//   tail_tile(t)     the current desc's last tile t, not a full one
+template <typename Desc, typename Enter, typename Leave, typename FullRun,
+          typename TailTile>
+__device__ __forceinline__ void walk_descs(
+    const Desc* __restrict__ descs, const uint64_t* __restrict__ tile_prefix,
+    uint32_t n, uint64_t begin, uint64_t end, Enter&& enter, Leave&& leave,
+    FullRun&& full_run, TailTile&& tail_tile) {
+  uint32_t i = wave_uniform(find_seg(tile_prefix, n, begin));
+  uint64_t cur_full, base_tile, next_boundary;
+  auto enter_desc = [&] {
+    cur_full = enter(descs[i]) / kTileBytes;
+    next_boundary = (i + 1 < n) ? wave_uniform(tile_prefix[i + 1]) : ~0ull;
+  };
+  enter_desc();
+  base_tile = wave_uniform(tile_prefix[i]);
+
+  uint64_t gt = begin;
+  while (gt < end) {
+    while (gt >= next_boundary) {
+      leave(i);
+      ++i;
+      base_tile = next_boundary;
+      enter_desc();
+    }
+    const uint64_t t = gt - base_tile;
+    // the desc's tiles inside this wave's range, and the full ones of them
+    const uint64_t stop =
+        (end < next_boundary ? end : next_boundary) - base_tile;
+    const uint64_t full_stop = stop < cur_full ? stop : cur_full;
+    if (t < full_stop) {
+      const uint64_t left = full_stop - t;
+      const uint32_t run = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
+      full_run(t, run);
+      gt += run;
+    } else {
+      tail_tile(t);
+      ++gt;
+    }
+  }
+  leave(i);
+}
+
+// The pipelined run of every batched walk: n >= 1 full tiles of the current
+// desc, from its tile t0, kDepth tiles deep (0: load, then fold). Counting
+// inside a run is 32-bit: scalar compares, where 64-bit ones take the VALU.
+// The walk brings, each for the desc's tile t:
+//   load(t)        -> Slot: issue the tile's loads
+//   consume(s, t)  the fragments' last uses, the store and the MFMAs; returns
+//                  the projections
+//   fold(acc, t)   the long VALU part of the hash
+// t0 is added HERE. Handed the count alone, with t0 added in the callables,
+// the compiler splits a slot into a scalar part and (k*64 | lane) and keeps
+// the latter in registers throughout: 6 VGPRs, an occupancy step of the put
+// and get kernels (profiles/walk_skeleton_checks.md).
+template <int kDepth, typename Slot, typename Load, typename Consume,
+          typename Fold>
+__device__ __forceinline__ void run_tiles(uint64_t t0, uint32_t n, Load&& load,
+                                          Consume&& consume, Fold&& fold) {
+  // tiles [i, stop) of the run one by one: load, consume, fold
+  auto plain = [&](uint32_t i, uint32_t stop) {
+    for (; i < stop; ++i) fold(consume(load(t0 + i), t0 + i), t0 + i);
+  };
+  // no pipeline, or a run too short for one
+  if (kDepth == 0 || n < 2u * kDepth) {
+    plain(0, n);
+    return;
+  }
+  if constexpr (kDepth > 0) {
+    // buf[k] holds tile i+k, then tile i+k+kDepth: the slots rotate by
+    // unrolling, no fragment is ever moved between registers.
+    Slot buf[kDepth];
+    // One step: consume tile i+k, refill its slot kDepth tiles ahead, then
+    // the long fold. The scheduling barriers keep that order. A load
+    // hoisted above the consumption needs a second register set, and the
+    // copy back into the slot waits for the load it was meant to leave in
+    // flight; loads issued in another order than their slots are used
+    // make the counted wait of the first slot a full one.
+    auto step = [&](uint32_t k, uint32_t i, bool refill) {
+      const auto acc = consume(buf[k], t0 + i + k);
+      __builtin_amdgcn_sched_barrier(0);
+      if (refill) buf[k] = load(t0 + i + k + kDepth);
+      __builtin_amdgcn_sched_barrier(0);
+      fold(acc, t0 + i + k);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) {
+      buf[k] = load(t0 + k);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // Steady state: every step issues one load. The first group stands in
+    // front of the loop so that the loop is entered with the same loads
+    // and stores in flight as its back edge brings, and its waits count
+    // for the steady state, not for the prologue.
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+    for (i = kDepth; i + 2u * kDepth <= n; i += kDepth) {
+#pragma unroll
+      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
+    }
+    // kDepth <= n - i < 2*kDepth tiles left: drain the slots, and the
+    // fewer than kDepth tiles behind them go one by one
+#pragma unroll
+    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, false);
+    plain(i + kDepth, n);
+  }
+}
 
 // What a wave of the walk's warm tail does plainly (digest_walk, kWarm).
 constexpr int kWarmNone = 0;
 constexpr int kWarmStores = 1;
 constexpr int kWarmLoads = 2;
 
-// The batched tile walk. One desc = one contiguous run of bytes that starts
-// on a tile boundary: a whole object at object-offset 0 (CopyDesc), or a
-// segment of a striped object (StripeSeg). tile_prefix[i] is the global index
-// of desc i's first 1-KiB tile. Each wave owns a CONTIGUOUS range of global
-// tiles, so desc switches (a 64-lane reduction + one atomic) happen only at
-// desc boundaries inside the range; the current descriptor/boundary live in
-// scalar registers (a per-tile global load of descs[]/tile_prefix[]
-// serializes on L2 latency), and the range is cut into runs of full tiles of
-// one desc plus at most one tail tile per desc. Every tile is loaded once
-// with the MFMA A-fragment lane map (fully coalesced) and hashed in
-// registers; out[i] accumulates desc i's partial sums and is finalized by a
-// follow-up kernel.
+// The batched digest walk over walk_descs: a desc is a whole object at
+// object-offset 0 (CopyDesc) or a segment of a striped object (StripeSeg).
+// Every tile is loaded once with the MFMA A-fragment lane map (fully
+// coalesced) and hashed in registers; leaving a desc costs a 64-lane
+// reduction + one atomic. out[i] accumulates desc i's partial sums and is
+// finalized by a follow-up kernel.
 //   kCopy:     also store the fragment to dst with the same lane map.
 //   kDepth:    software pipeline over a run of full tiles — a tile is stored
 //              and handed to the MFMA, its slot is refilled with the tile
@@ -295,44 +430,29 @@ __device__ __forceinline__ void digest_walk(
     uint64_t warm_begin = ~0ull) {
   constexpr bool kStripe = std::is_same_v<Desc, StripeSeg>;
   const int lane = threadIdx.x & 63;
-  // the wave index and all that follows from it: ranges, boundaries and the
-  // descriptor are the same in every lane, and the compiler is told so
-  const uint32_t wave = wave_uniform(threadIdx.x >> 6);
-  const uint64_t gwave =
-      static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
-  const uint64_t per = (total_tiles + nwaves - 1) / nwaves;
-  const uint64_t begin = gwave * per;
-  const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
-  if (begin >= total_tiles) return;
+  uint64_t begin, end;
+  if (!wave_tile_range(total_tiles, begin, end)) return;
   [[maybe_unused]] const bool warm = begin >= warm_begin;
 
   const i32x4 b_frag = load_b_frag(lane);
   const WReg wr = load_w_reg(lane);
   const uint32_t lane_off = lane_tile_offset(lane);
 
-  uint32_t oi = wave_uniform(find_seg(tile_prefix, nobjs, begin));
   const uint8_t* src;
   uint8_t* dst;
-  uint64_t nbytes, cur_full;
+  uint64_t nbytes;
   [[maybe_unused]] uint64_t first_slot = 0;  // StripeSeg: first_tile * 64
   [[maybe_unused]] uint32_t obj = 0;
-  uint64_t base_tile, next_boundary;
-  auto enter_object = [&] {
-    const Desc d = descs[oi];
+  auto enter = [&](const Desc& d) {
     src = wave_uniform(static_cast<const uint8_t*>(d.src));
     dst = wave_uniform(static_cast<uint8_t*>(d.dst));
     nbytes = wave_uniform(d.nbytes);
-    cur_full = nbytes / kTileBytes;
     if constexpr (kStripe) {
       first_slot = wave_uniform(d.first_tile) * 64;
       obj = wave_uniform(d.obj);
     }
-    next_boundary =
-        (oi + 1 < nobjs) ? wave_uniform(tile_prefix[oi + 1]) : ~0ull;
+    return nbytes;
   };
-  enter_object();
-  base_tile = wave_uniform(tile_prefix[oi]);
 
   uint64_t h = 0;
   [[maybe_unused]] uint64_t ho = 0;  // StripeSeg: the object-slot sum
@@ -343,6 +463,12 @@ __device__ __forceinline__ void digest_walk(
     if (lane == 0 && ho != 0) atomicAdd(&obj_out[obj], ho);
     ho = 0;
   };
+  auto leave = [&](uint32_t i) {
+    h = wave_sum_u64(h);
+    if (lane == 0 && h != 0) atomicAdd(&out[i], h);
+    if constexpr (kStripe) flush_object();
+    h = 0;
+  };
   // tile t of the current desc, projected: the VALU part of its hash
   auto fold = [&](const i32x16& acc, uint64_t t) {
     const uint64_t f = fold_group(acc, wr);
@@ -351,114 +477,39 @@ __device__ __forceinline__ void digest_walk(
     if constexpr (kStripe)
       if (first_slot != 0) ho += mix_slot(f, first_slot + slot);
   };
-  // n >= 1 full tiles of the current desc, from its tile t0. Counting inside
-  // a run is 32-bit: scalar compares, where 64-bit ones take the VALU.
-  // warm_tag: the run belongs to a wave of the warm tail.
-  auto full_run = [&](auto warm_tag, uint64_t t0, uint32_t n) {
-    constexpr bool kWarmRun = decltype(warm_tag)::value;
-    constexpr bool kNtSt = !(kWarmRun && (kWarm & kWarmStores));
-    constexpr bool kNtLd = kNtLoads && !(kWarmRun && (kWarm & kWarmLoads));
-    const uint8_t* s = src + t0 * kTileBytes;
-    // the fragment's last uses: the store and the MFMA
-    auto consume = [&](const i32x4& a, uint32_t i) {
-      if constexpr (kCopy)
-        store_a_frag<kNtSt>(dst + (t0 + i) * kTileBytes, lane_off, a);
-      return project_tile(a, b_frag);
+  // n >= 1 full tiles of the current desc, from its tile t0
+  auto full_run = [&](uint64_t t0, uint32_t n) {
+    // warm_tag: the run belongs to a wave of the warm tail
+    auto body = [&](auto warm_tag) {
+      constexpr bool kWarmRun = decltype(warm_tag)::value;
+      constexpr bool kNtSt = !(kWarmRun && (kWarm & kWarmStores));
+      constexpr bool kNtLd = kNtLoads && !(kWarmRun && (kWarm & kWarmLoads));
+      run_tiles<kDepth, i32x4>(
+          t0, n,
+          [&](uint64_t t) {
+            return load_a_frag<kNtLd>(src + t * kTileBytes, lane_off);
+          },
+          // the fragment's last uses: the store and the MFMA
+          [&](const i32x4& a, uint64_t t) {
+            if constexpr (kCopy)
+              store_a_frag<kNtSt>(dst + t * kTileBytes, lane_off, a);
+            return project_tile(a, b_frag);
+          },
+          fold);
     };
-    // tiles [i, stop) of the run one by one: load, consume, fold
-    auto plain = [&](uint32_t i, uint32_t stop) {
-      for (; i < stop; ++i)
-        fold(consume(load_a_frag<kNtLd>(s + uint64_t{i} * kTileBytes, lane_off),
-                     i),
-             t0 + i);
-    };
-    // the walk without a pipeline, or a run too short for one
-    if (kDepth == 0 || n < 2u * kDepth) {
-      plain(0, n);
-      return;
-    }
-    if constexpr (kDepth > 0) {
-      // buf[k] holds tile i+k, then tile i+k+kDepth: the slots rotate by
-      // unrolling, no fragment is ever moved between registers.
-      i32x4 buf[kDepth];
-      // One step: consume tile i+k, refill its slot kDepth tiles ahead, then
-      // the long fold. The scheduling barriers keep that order. A load
-      // hoisted above the consumption needs a second register set, and the
-      // copy back into the slot waits for the load it was meant to leave in
-      // flight; loads issued in another order than their slots are used
-      // make the counted wait of the first slot a full one.
-      auto step = [&](uint32_t k, uint32_t i, bool refill) {
-        const i32x16 acc = consume(buf[k], i + k);
-        __builtin_amdgcn_sched_barrier(0);
-        if (refill)
-          buf[k] = load_a_frag<kNtLd>(
-              s + uint64_t{i + k + kDepth} * kTileBytes, lane_off);
-        __builtin_amdgcn_sched_barrier(0);
-        fold(acc, t0 + i + k);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-#pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) {
-        buf[k] = load_a_frag<kNtLd>(s + uint64_t{k} * kTileBytes, lane_off);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // Steady state: every step issues one load. The first group stands in
-      // front of the loop so that the loop is entered with the same loads
-      // and stores in flight as its back edge brings, and its waits count
-      // for the steady state, not for the prologue.
-      uint32_t i = 0;
-#pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
-      for (i = kDepth; i + 2u * kDepth <= n; i += kDepth) {
-#pragma unroll
-        for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
-      }
-      // kDepth <= n - i < 2*kDepth tiles left: drain the slots, and the
-      // fewer than kDepth tiles behind them go one by one
-#pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, false);
-      plain(i + kDepth, n);
-    }
+    if constexpr (kWarm != kWarmNone)
+      if (warm) return body(std::true_type{});
+    body(std::false_type{});
   };
-
-  uint64_t gt = begin;
-  while (gt < end) {
-    while (gt >= next_boundary) {
-      h = wave_sum_u64(h);
-      if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
-      if constexpr (kStripe) flush_object();
-      h = 0;
-      ++oi;
-      base_tile = next_boundary;
-      enter_object();
-    }
-    const uint64_t t = gt - base_tile;
-    // the desc's tiles inside this wave's range, and the full ones of them
-    const uint64_t stop =
-        (end < next_boundary ? end : next_boundary) - base_tile;
-    const uint64_t full_stop = stop < cur_full ? stop : cur_full;
-    if (t < full_stop) {
-      const uint64_t left = full_stop - t;
-      const uint32_t n = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
-      if constexpr (kWarm != kWarmNone) {
-        if (warm) full_run(std::true_type{}, t, n);
-        else full_run(std::false_type{}, t, n);
-      } else {
-        full_run(std::false_type{}, t, n);
-      }
-      gt += n;
-    } else {
-      // tail tile: zero-padded hash, byte-guarded store
-      const uint64_t toff = t * kTileBytes;
-      const i32x4 a = load_a_frag_guarded(src, toff, nbytes, lane_off);
-      if constexpr (kCopy) store_a_frag_guarded(dst, toff, nbytes, lane_off, a);
-      fold(project_tile(a, b_frag), t);
-      ++gt;
-    }
-  }
-  h = wave_sum_u64(h);
-  if (lane == 0 && h != 0) atomicAdd(&out[oi], h);
-  if constexpr (kStripe) flush_object();
+  // zero-padded hash, byte-guarded store
+  auto tail_tile = [&](uint64_t t) {
+    const uint64_t toff = t * kTileBytes;
+    const i32x4 a = load_a_frag_guarded(src, toff, nbytes, lane_off);
+    if constexpr (kCopy) store_a_frag_guarded(dst, toff, nbytes, lane_off, a);
+    fold(project_tile(a, b_frag), t);
+  };
+  walk_descs(descs, tile_prefix, nobjs, begin, end, enter, leave, full_run,
+             tail_tile);
 }
 
 // Tiles per load stream (old and new) that the patch walk keeps in flight:
@@ -466,10 +517,10 @@ __device__ __forceinline__ void digest_walk(
 // fragment registers per tile.
 constexpr int kPatchDepth = 2;
 
-// The sibling walk of the in-place range patch (patch.hip). One run = one
-// PatchSeg: new bytes at src that replace the old ones at dst, from a tile
-// boundary of the run's shard and of its object. The ranges, the boundary
-// bookkeeping and the tile helpers are digest_walk's; what differs is that
+// The walk of the in-place range patch (patch.hip) over walk_descs. One run =
+// one PatchSeg: new bytes at src that replace the old ones at dst, from a
+// tile boundary of the run's shard and of its object. The ranges and the
+// boundary loop are the ones digest_walk stands on; what differs is that
 // every tile is loaded twice — old from dst, new from src — both fragments
 // go through the MFMA and the group fold, and the sums take the DIFFERENCE
 // mix_slot(f_new, slot) − mix_slot(f_old, slot) (u64 wraparound):
@@ -497,44 +548,31 @@ __device__ __forceinline__ void patch_walk(
     unsigned long long* __restrict__ obj_acc) {
   static_assert(kDepth >= 1);
   const int lane = threadIdx.x & 63;
-  const uint32_t wave = wave_uniform(threadIdx.x >> 6);
-  const uint64_t gwave =
-      static_cast<uint64_t>(blockIdx.x) * kWavesPerBlock + wave;
-  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kWavesPerBlock;
-  const uint64_t per = (total_tiles + nwaves - 1) / nwaves;
-  const uint64_t begin = gwave * per;
-  const uint64_t end = begin + per < total_tiles ? begin + per : total_tiles;
-  if (begin >= total_tiles) return;
+  uint64_t begin, end;
+  if (!wave_tile_range(total_tiles, begin, end)) return;
 
   const i32x4 b_frag = load_b_frag(lane);
   const WReg wr = load_w_reg(lane);
   const uint32_t lane_off = lane_tile_offset(lane);
 
-  uint32_t si = wave_uniform(find_seg(tile_prefix, nseg, begin));
   const uint8_t* src;
   uint8_t* dst;
-  uint64_t nbytes, cur_full, shard_slot, obj_slot;
+  uint64_t nbytes, shard_slot, obj_slot;
   uint32_t shard, obj;
-  uint64_t base_tile, next_boundary;
-  auto enter_run = [&] {
-    const PatchSeg d = segs[si];
+  auto enter = [&](const PatchSeg& d) {
     src = wave_uniform(static_cast<const uint8_t*>(d.src));
     dst = wave_uniform(static_cast<uint8_t*>(d.dst));
     nbytes = wave_uniform(d.nbytes);
-    cur_full = nbytes / kTileBytes;
     shard_slot = wave_uniform(d.shard_tile) * 64;
     obj_slot = wave_uniform(d.obj_tile) * 64;
     shard = wave_uniform(d.shard);
     obj = wave_uniform(d.obj);
-    next_boundary =
-        (si + 1 < nseg) ? wave_uniform(tile_prefix[si + 1]) : ~0ull;
+    return nbytes;
   };
-  enter_run();
-  base_tile = wave_uniform(tile_prefix[si]);
 
   uint64_t hs = 0, ho = 0;  // the shard-slot and object-slot differences
   // leaving a run: its shares of the two accumulators
-  auto flush = [&] {
+  auto leave = [&](uint32_t) {
     hs = wave_sum_u64(hs);
     if (shard_slot != obj_slot) ho = wave_sum_u64(ho);
     else ho = hs;
@@ -542,17 +580,21 @@ __device__ __forceinline__ void patch_walk(
     if (lane == 0 && ho != 0) atomicAdd(&obj_acc[obj], ho);
     hs = ho = 0;
   };
+  // a tile's old and new bytes: the fragments and their projections
+  struct Pair {
+    i32x4 o, n;
+  };
+  struct Acc {
+    i32x16 o, n;
+  };
   // tile t of the current run, old and new projected
-  auto fold = [&](const i32x16& acc_old, const i32x16& acc_new, uint64_t t) {
-    const uint64_t f_old = fold_group(acc_old, wr);
-    const uint64_t f_new = fold_group(acc_new, wr);
+  auto fold = [&](const Acc& acc, uint64_t t) {
+    const uint64_t f_old = fold_group(acc.o, wr);
+    const uint64_t f_new = fold_group(acc.n, wr);
     const uint64_t slot = t * 64 + lane;
     hs += mix_slot(f_new, shard_slot + slot) - mix_slot(f_old, shard_slot + slot);
     if (shard_slot != obj_slot)
       ho += mix_slot(f_new, obj_slot + slot) - mix_slot(f_old, obj_slot + slot);
-  };
-  struct Pair {
-    i32x4 o, n;
   };
   // old first, then new: see "Ordering" above
   auto load_pair = [&](uint64_t tile) {
@@ -565,73 +607,26 @@ __device__ __forceinline__ void patch_walk(
   };
   // n >= 1 full tiles of the current run, from its tile t0
   auto full_run = [&](uint64_t t0, uint32_t n) {
-    auto plain = [&](uint32_t i, uint32_t stop) {
-      for (; i < stop; ++i) {
-        const Pair p = load_pair(t0 + i);
-        store_a_frag(dst + (t0 + i) * kTileBytes, lane_off, p.n);
-        fold(project_tile(p.o, b_frag), project_tile(p.n, b_frag), t0 + i);
-      }
-    };
-    if (n < 2u * kDepth) {
-      plain(0, n);
-      return;
-    }
-    // buf[k] holds tile i+k, then tile i+k+kDepth, as in digest_walk
-    Pair buf[kDepth];
-    auto step = [&](uint32_t k, uint32_t i, bool refill) {
-      store_a_frag(dst + (t0 + i + k) * kTileBytes, lane_off, buf[k].n);
-      const i32x16 acc_old = project_tile(buf[k].o, b_frag);
-      const i32x16 acc_new = project_tile(buf[k].n, b_frag);
-      __builtin_amdgcn_sched_barrier(0);
-      if (refill) buf[k] = load_pair(t0 + i + k + kDepth);
-      __builtin_amdgcn_sched_barrier(0);
-      fold(acc_old, acc_new, t0 + i + k);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-#pragma unroll
-    for (uint32_t k = 0; k < kDepth; ++k) buf[k] = load_pair(t0 + k);
-    uint32_t i = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
-    for (i = kDepth; i + 2u * kDepth <= n; i += kDepth) {
-#pragma unroll
-      for (uint32_t k = 0; k < kDepth; ++k) step(k, i, true);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kDepth; ++k) step(k, i, false);
-    plain(i + kDepth, n);
+    run_tiles<kDepth, Pair>(
+        t0, n, load_pair,
+        [&](const Pair& p, uint64_t t) {
+          store_a_frag(dst + t * kTileBytes, lane_off, p.n);
+          return Acc{project_tile(p.o, b_frag), project_tile(p.n, b_frag)};
+        },
+        fold);
   };
-
-  uint64_t gt = begin;
-  while (gt < end) {
-    while (gt >= next_boundary) {
-      flush();
-      ++si;
-      base_tile = next_boundary;
-      enter_run();
-    }
-    const uint64_t t = gt - base_tile;
-    const uint64_t stop =
-        (end < next_boundary ? end : next_boundary) - base_tile;
-    const uint64_t full_stop = stop < cur_full ? stop : cur_full;
-    if (t < full_stop) {
-      const uint64_t left = full_stop - t;
-      const uint32_t n = left < kMaxRun ? static_cast<uint32_t>(left) : kMaxRun;
-      full_run(t, n);
-      gt += n;
-    } else {
-      // tail tile: byte-guarded loads of both, zero-padded; every load has
-      // returned before the first byte is stored
-      const uint64_t toff = t * kTileBytes;
-      const i32x4 a_old = load_a_frag_guarded(dst, toff, nbytes, lane_off);
-      const i32x4 a_new = load_a_frag_guarded(src, toff, nbytes, lane_off);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      store_a_frag_guarded(dst, toff, nbytes, lane_off, a_new);
-      fold(project_tile(a_old, b_frag), project_tile(a_new, b_frag), t);
-      ++gt;
-    }
-  }
-  flush();
+  // byte-guarded loads of both, zero-padded; every load has returned before
+  // the first byte is stored
+  auto tail_tile = [&](uint64_t t) {
+    const uint64_t toff = t * kTileBytes;
+    const i32x4 a_old = load_a_frag_guarded(dst, toff, nbytes, lane_off);
+    const i32x4 a_new = load_a_frag_guarded(src, toff, nbytes, lane_off);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    store_a_frag_guarded(dst, toff, nbytes, lane_off, a_new);
+    fold(Acc{project_tile(a_old, b_frag), project_tile(a_new, b_frag)}, t);
+  };
+  walk_descs(segs, tile_prefix, nseg, begin, end, enter, leave, full_run,
+             tail_tile);
 }
 
 }  // namespace blackbird::gpu::dev

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <vector>
 
 #include "batch_launch.hip.h"
 #include "blackbird/gpu/gpu_kernels.h"
@@ -75,9 +76,10 @@ Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
                          hipStream_t stream) {
   BB_RETURN_IF_ERROR(check_patch_segs(segs, nseg, shard_lens, shard_old, nshard,
                                       obj_sizes, obj_old, nobj));
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < nseg; ++i)
-    total += (segs[i].nbytes + digest::kTileBytes - 1) / digest::kTileBytes;
+  // before any HIP call: a launch without a tile needs no device
+  std::vector<uint64_t> prefix(nseg);
+  const uint64_t total =
+      fill_prefix(segs, nseg, digest::kTileBytes, prefix.data());
   if (total == 0) {  // nothing patched: every digest stands
     if (nshard) std::memcpy(out_shard_digests, shard_old, nshard * sizeof(uint64_t));
     if (nobj) std::memcpy(out_obj_digests, obj_old, nobj * sizeof(uint64_t));
@@ -94,12 +96,7 @@ Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
   void* dev = g_patch_stage.device;
 
   std::memcpy(b.segs(host), segs, nseg * sizeof(PatchSeg));
-  uint64_t* h_prefix = b.prefix(host);
-  uint64_t at = 0;
-  for (uint32_t i = 0; i < nseg; ++i) {
-    h_prefix[i] = at;
-    at += (segs[i].nbytes + digest::kTileBytes - 1) / digest::kTileBytes;
-  }
+  std::memcpy(b.prefix(host), prefix.data(), nseg * sizeof(uint64_t));
   uint64_t* h_lens = b.lens(host);
   uint64_t* h_acc = b.acc(host);
   for (uint32_t i = 0; i < nshard; ++i) {

@@ -70,13 +70,7 @@ uint64_t fill_stripe_block(const StripeBlock& b, void* host,
                            const StripeSeg* segs, const uint64_t* obj_sizes) {
   std::memcpy(b.segs(host), segs, b.nseg * sizeof(StripeSeg));
   std::memcpy(b.obj_sizes(host), obj_sizes, b.nobj * sizeof(uint64_t));
-  uint64_t* h_prefix = b.prefix(host);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < b.nseg; ++i) {
-    h_prefix[i] = total;
-    total += (segs[i].nbytes + digest::kTileBytes - 1) / digest::kTileBytes;
-  }
-  return total;
+  return fill_prefix(segs, b.nseg, digest::kTileBytes, b.prefix(host));
 }
 
 // The striped step over an uploaded block: zero both accumulator arrays →

@@ -16,13 +16,21 @@ empty):
                   and the last ranges start in the last descriptor
 
 Every case runs through checksum_device_batch, fused_put, fused_put_plan
-(three replays) and fused_stripe: digests bit-exact against gpu.checksum_cpu,
-destination bytes exact including the pre-filled gaps. The layout is that of
-test_gpu_walk_pipeline.py: objects at 16-byte-aligned offsets of one
-allocation with 16 bytes of gap behind each, 0x5A in the source gaps, the
-destination pre-filled with 0xA5, the last object ending where both
-allocations end. fused_stripe takes objects of more than 64 tiles as two
+(three replays), fused_stripe and fused_patch: digests bit-exact against
+gpu.checksum_cpu, destination bytes exact including the pre-filled gaps. The
+layout is that of test_gpu_walk_pipeline.py: objects at 16-byte-aligned
+offsets of one allocation with 16 bytes of gap behind each, 0x5A in the
+source gaps, the destination pre-filled with 0xA5, the last object ending
+where both allocations end. fused_stripe takes objects of more than 64 tiles as two
 segments, the second with first_tile != 0.
+
+fused_patch patches every non-empty object whole, over old random bytes of
+the same sizes in the destination (a second seed; the old digests are
+checksum_cpu of them). Its runs are the stripe entry's segments, each a shard
+of its own: the second run of a long object has shard_tile 0 and obj_tile at
+the cut, so both mixes run. A zero-byte object is registered nowhere (a
+recorded digest of 0 is refused); its zero-length run names the shard and
+the object of a neighbour.
 """
 import numpy as np
 import pytest
@@ -36,7 +44,7 @@ PAD = 0xA5
 gpu = bb.core.gpu
 
 ENTRIES = ["checksum_device_batch", "fused_put", "fused_put_plan",
-           "fused_stripe"]
+           "fused_stripe", "fused_patch"]
 CASES = ["odd_last_range", "one_object", "empty_ranges", "small_objects"]
 
 # sizes of 1-3 tiles: whole tiles, 1-byte and 1023-byte tails, and nothing;
@@ -88,6 +96,47 @@ class _Batch:
                                   gpu.checksum_cpu(blob[cut * TILE:])))
         self.src_image = src.tobytes()
         self.dst_image = dst.tobytes()
+        self.seed = seed
+        self._patch = None
+
+    def patch(self):
+        """What fused_patch needs on top, made once: (the destination's old
+        image, runs as (segment index, shard_tile, obj_tile, shard, obj),
+        shard lengths, old shard digests, object sizes, old object digests,
+        expected shard digests, expected object digests)."""
+        if self._patch is None:
+            old = np.random.default_rng(self.seed + 100).integers(
+                0, 256, sum(self.sizes), dtype=np.uint8)
+            img = np.full(self.span, PAD, dtype=np.uint8)
+            start = np.concatenate(([0], np.cumsum(self.sizes)))
+            obj_of, sizes, obj_old, obj_want = {}, [], [], []
+            for i, (o, s) in enumerate(zip(self.offs, self.sizes)):
+                if s:
+                    blob = old[start[i]:start[i] + s]
+                    img[o:o + s] = blob
+                    obj_of[i] = len(sizes)
+                    sizes.append(s)
+                    obj_old.append(gpu.checksum_cpu(blob))
+                    obj_want.append(self.want[i])
+            runs, lens, shard_old, shard_want = [], [], [], []
+            for k, (i, o, n, first, d) in enumerate(self.segs):
+                if n:
+                    at = start[i] + first * TILE
+                    runs.append((k, 0, first, len(lens), obj_of[i]))
+                    lens.append(n)
+                    shard_old.append(gpu.checksum_cpu(old[at:at + n]))
+                    shard_want.append(d)
+                else:
+                    runs.append(None)
+            # a zero-length run: the nearest run's shard and object
+            live = [r for r in runs if r]
+            for k, r in enumerate(runs):
+                if r is None:
+                    near = next((q for q in runs[k::-1] if q), live[0])
+                    runs[k] = (k, 0, 0, near[3], near[4])
+            self._patch = (img.tobytes(), runs, lens, shard_old, sizes,
+                           obj_old, shard_want, obj_want)
+        return self._patch
 
     def tiles(self):
         return sum(_tiles(s) for s in self.sizes)
@@ -147,7 +196,8 @@ def test_ranges(name, entry):
     src, dst = gpu.malloc(b.span), gpu.malloc(b.span)
     try:
         gpu.upload(src, b.src_image)
-        gpu.upload(dst, bytes([PAD]) * b.span)
+        gpu.upload(dst, b.patch()[0] if entry == "fused_patch"
+                   else bytes([PAD]) * b.span)
         descs = [(src + o, dst + o, s) for o, s in zip(b.offs, b.sizes)]
         if entry == "checksum_device_batch":
             _check(gpu.checksum_device_batch([(s, n) for s, _, n in descs]),
@@ -159,6 +209,15 @@ def test_ranges(name, entry):
             assert len(steps) == 3
             assert steps[1] == steps[0] and steps[2] == steps[0]
             _check(steps[0], b.want, entry)
+        elif entry == "fused_patch":
+            _, runs, lens, shard_old, sizes, obj_old, shard_want, obj_want = \
+                b.patch()
+            shard, obj = gpu.fused_patch(
+                [(src + b.segs[k][1], dst + b.segs[k][1], b.segs[k][2],
+                  st, ot, sh, ob) for k, st, ot, sh, ob in runs],
+                lens, shard_old, sizes, obj_old)
+            _check(shard, shard_want, "shards")
+            _check(obj, obj_want, "objects")
         else:
             seg, obj = gpu.fused_stripe(
                 [(src + o, dst + o, n, first, i)
