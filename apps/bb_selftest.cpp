@@ -5,8 +5,12 @@
 // mutation, a keystone put/get/remove storm with maintenance passes, the
 // client placement cache with session bindings racing recorders and erasers,
 // and the clients' batch fan-out.
+#include <unistd.h>
+
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -14,6 +18,7 @@
 #include "blackbird/allocation/range_allocator.h"
 #include "blackbird/client/batch_util.h"
 #include "blackbird/client/placement_cache.h"
+#include "blackbird/client/pool_mapper.h"
 #include "blackbird/coord/coord.h"
 #include "blackbird/keystone/keystone_rpc.h"
 #include "blackbird/keystone/keystone_service.h"
@@ -746,6 +751,70 @@ void fan_out_storm() {
   for (auto& t : ts) t.join();
 }
 
+// The pool resolver under its callers' concurrency: views of two RAM_CPU
+// pools taken by registry entry and by shm name through one shared mapper,
+// each thread copying through view.base in a 4 KiB range of its own, while
+// the registry gains and loses an unrelated entry.
+void pool_view_storm() {
+  constexpr uint64_t kPool = 1 << 20, kRange = 4096;
+  constexpr int kThreads = 6;
+  const PoolId ids[2] = {"storm_a", "storm_b"};
+  std::unique_ptr<StorageBackend> pools[2];
+  for (int p = 0; p < 2; ++p) {
+    PoolConfig pc;
+    pc.pool_id = ids[p];
+    pc.storage_class = StorageClass::RAM_CPU;
+    pc.size_bytes = kPool;
+    auto b = create_storage_backend(pc, "selftest" + std::to_string(getpid()));
+    CHECK(b.ok() && b.value()->initialize().ok());
+    if (failures) return;
+    pools[p] = std::move(b.value());
+    LocalPools::inst().add(ids[p], pools[p]->base_ptr(), kPool, false, -1,
+                           pools[p].get());
+  }
+  PoolMapper mapper;
+  std::atomic<bool> stop{false};
+  std::thread churn([&] {
+    static uint8_t unrelated[64];
+    while (!stop.load()) {
+      LocalPools::inst().add("storm_tmp", unrelated, sizeof(unrelated), false, -1);
+      CHECK(PoolMapper::local("storm_tmp").base == unrelated);
+      LocalPools::inst().remove("storm_tmp");
+    }
+  });
+  std::vector<std::thread> ts;
+  for (int t = 0; t < kThreads; ++t)
+    ts.emplace_back([&, t] {
+      std::vector<uint8_t> out(kRange), in(kRange);
+      for (int i = 0; i < 400; ++i) {
+        const int p = i & 1;
+        PoolView v = (t & 1) ? mapper.remote(pools[p]->access_info())
+                             : PoolMapper::local(ids[p]);
+        CHECK(v.base && !v.device && v.size == kPool);
+        CHECK((v.local == pools[p].get()) == !(t & 1));
+        const uint64_t off = t * kRange;
+        CHECK(v.contains(off, kRange) && !v.contains(kPool - kRange, 2 * kRange));
+        if (!v.base) return;
+        std::fill(out.begin(), out.end(), static_cast<uint8_t>(t * 31 + i));
+        std::memcpy(v.base + off, out.data(), kRange);
+        std::memcpy(in.data(), v.base + off, kRange);
+        CHECK(in == out);
+      }
+    });
+  for (auto& t : ts) t.join();
+  stop = true;
+  churn.join();
+  CHECK(!PoolMapper::local("storm_tmp").base);
+  for (int p = 0; p < 2; ++p) {
+    // what a thread wrote through either mapping, the backend reads
+    std::vector<uint8_t> got(kRange);
+    CHECK(pools[p]->read((kThreads - 1) * kRange, got.data(), kRange).ok());
+    CHECK(got[0] == static_cast<uint8_t>((kThreads - 1) * 31 + 398 + p));
+    LocalPools::inst().remove(ids[p]);
+    CHECK(!PoolMapper::local(ids[p]).base);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -768,6 +837,8 @@ int main() {
   placement_cache_storm();
   std::printf("fan_out_storm...\n");
   fan_out_storm();
+  std::printf("pool_view_storm...\n");
+  pool_view_storm();
   if (failures) {
     std::printf("SELFTEST FAILED (%d checks)\n", failures);
     return 1;

@@ -8,6 +8,7 @@
 
 #include "blackbird/client/client.h"
 #include "blackbird/client/gpu_client.h"
+#include "blackbird/client/pool_mapper.h"
 #include "blackbird/client/shuffle.h"
 #include "blackbird/gpu/gpu_kernels.h"
 #include "blackbird/keystone/keystone_rpc.h"
@@ -307,6 +308,38 @@ void bind_store(py::module_& m) {
     return b;
   });
 
+  // Test-only: the pool resolver as the clients and the transfer engine call
+  // it. read/write go through `base` of a host view.
+  py::class_<PoolView>(m, "PoolViewForTest")
+      .def(py::init([](uint64_t size) {
+             PoolView v;
+             v.size = size;
+             return v;
+           }),
+           py::arg("size"))
+      .def_property_readonly(
+          "base", [](const PoolView& v) { return reinterpret_cast<uintptr_t>(v.base); })
+      .def_readonly("size", &PoolView::size)
+      .def_readonly("device", &PoolView::device)
+      .def_property_readonly(
+          "local", [](const PoolView& v) { return v.local; },
+          py::return_value_policy::reference)
+      .def("contains", &PoolView::contains)
+      .def("write", [](const PoolView& v, uint64_t off, const std::string& data) {
+        if (!v.base || v.device || !v.contains(off, data.size()))
+          throw std::runtime_error("not a host range of this view");
+        std::memcpy(v.base + off, data.data(), data.size());
+      })
+      .def("read", [](const PoolView& v, uint64_t off, uint64_t len) {
+        if (!v.base || v.device || !v.contains(off, len))
+          throw std::runtime_error("not a host range of this view");
+        return py::bytes(reinterpret_cast<const char*>(v.base + off), len);
+      });
+  py::class_<PoolMapper>(m, "PoolMapperForTest")
+      .def(py::init<>())
+      .def_static("local", &PoolMapper::local)
+      .def("remote", &PoolMapper::remote);
+
   py::class_<WorkerService>(m, "WorkerService")
       .def(py::init([](const WorkerConfig& cfg,
                        std::shared_ptr<coord::CoordService> coord) {
@@ -510,6 +543,9 @@ void bind_store(py::module_& m) {
            py::keep_alive<1, 2>())
       .def("init", [](GpuClient& g) { unwrap_void(g.init()); },
            py::call_guard<py::gil_scoped_release>())
+      .def("pool_base_for_test", [](GpuClient& g, const std::string& pool_id) {
+        return reinterpret_cast<uintptr_t>(g.pool_base_for_test(pool_id));
+      })
       .def("set_fused_copy", &GpuClient::set_fused_copy)
       .def("set_warm_tail_bytes", &GpuClient::set_warm_tail_bytes,
            py::arg("bytes"))

@@ -193,6 +193,16 @@ Result<void> device_copy(void* pool, UserPtr<Write> user, uint64_t n) {
     return gpu::copy_sync(user, pool, n, hipMemcpyDeviceToHost);
 }
 
+// One-sided copy through a resolved view; only a device copy can fail.
+template <bool Write>
+Result<void> view_copy(const PoolView& v, const ShardPlacement& s,
+                       UserPtr<Write> user) {
+  void* pool = v.base + s.offset;
+  if (v.device) return device_copy<Write>(pool, user, s.length);
+  host_copy<Write>(pool, user, s.length);
+  return {};
+}
+
 template <bool Write>
 Result<void> tcp_copy(rpc::RpcClient& dc, const ShardPlacement& s,
                       UserPtr<Write> user, int timeout_ms) {
@@ -226,40 +236,24 @@ Result<void> Client::move_shard(const ShardPlacement& s, UserPtr<Write> user) {
   }
   const AccessInfo& a = s.access.endpoint.empty() ? resolved : s.access;
   if (!opts_.force_tcp) {
-    bool is_dev = false;
-    if (void* base = LocalPools::inst().lookup(s.pool_id, &is_dev)) {
-      void* pool = static_cast<uint8_t*>(base) + s.offset;
-      if (!is_dev) {
-        host_copy<Write>(pool, user, s.length);
-        return {};
-      }
+    PoolView v = PoolMapper::local(s.pool_id);
+    if (v.base) {
       // a failed device copy falls on to the later rungs
-      if (device_copy<Write>(pool, user, s.length).ok()) return {};
-    } else if (auto* be = LocalPools::inst().backend(s.pool_id)) {
+      if (view_copy<Write>(v, s, user).ok()) return {};
+    } else if (v.local) {
       // unmapped same-process pool (direct-IO NVMe tier): call the backend
       // directly instead of framing the bytes through TCP loopback
-      if constexpr (Write) return be->write(s.offset, user, s.length);
-      else return be->read(s.offset, user, s.length);
+      if constexpr (Write) return v.local->write(s.offset, user, s.length);
+      else return v.local->read(s.offset, user, s.length);
     }
-    if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
-      // one-sided host fast path. The pool's size is not known here: size 0
-      // maps the whole segment (sized by stat), cached by name.
-      if (void* base = mapper_->map_shm(a.shm_name, 0)) {
-        host_copy<Write>(static_cast<uint8_t*>(base) + s.offset, user,
-                         s.length);
-        return {};
-      }
-    }
-    if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty() &&
-        gpu::available()) {
-      if (void* base = mapper_->open_ipc(a.ipc_handle_hex, a.device_id)) {
-        auto e = device_copy<Write>(static_cast<uint8_t*>(base) + s.offset,
-                                    user, s.length);
-        if (e.ok()) return {};
-        BB_LOG(WARN) << "IPC " << (Write ? "write" : "read")
-                     << " failed: " << e.error().message
-                     << " — falling back to TCP";
-      }
+    // one-sided fast path into another process's pool
+    v = mapper_->remote(a);
+    if (v.base) {
+      auto e = view_copy<Write>(v, s, user);
+      if (e.ok()) return {};
+      BB_LOG(WARN) << "IPC " << (Write ? "write" : "read")
+                   << " failed: " << e.error().message
+                   << " — falling back to TCP";
     }
   }
   auto* dc = data_client(a.endpoint);
@@ -825,18 +819,16 @@ std::optional<std::vector<int32_t>> Client::try_host_session_put(
 }
 
 uint8_t* Client::host_pool_base(const PoolId& id, AccessInfo* access) {
-  bool is_dev = false;
-  if (void* b = LocalPools::inst().lookup(id, &is_dev)) {
-    // device pools stay on the shard path (write_shard/read_shard hipMemcpy)
-    return is_dev ? nullptr : static_cast<uint8_t*>(b);
+  PoolView v = PoolMapper::local(id);
+  if (!v.base) {
+    auto a = pool_access(id);
+    if (!a.ok()) return nullptr;
+    // device pools stay on the shard path (write_shard/read_shard
+    // hipMemcpy), which imports them when it first needs them
+    if (a->kind != AccessKind::HIP_IPC) v = mapper_->remote(a.value());
+    if (access) *access = std::move(a.value());
   }
-  auto a = pool_access(id);
-  if (!a.ok()) return nullptr;
-  uint8_t* out = nullptr;
-  if (a->kind == AccessKind::SHM && !a->shm_name.empty())
-    out = static_cast<uint8_t*>(mapper_->map_shm(a->shm_name, 0));
-  if (access) *access = std::move(a.value());
-  return out;
+  return v.device ? nullptr : v.base;
 }
 
 // Host twin of GpuClient::batch_put_device_v2: compact request, pool-table

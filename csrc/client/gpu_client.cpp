@@ -15,6 +15,7 @@
 #include "blackbird/client/pool_mapper.h"
 #include "blackbird/common/trace.h"
 #include "blackbird/common/log.h"
+#include "blackbird/gpu/hip_check.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/worker/storage_backend.h"
 
@@ -23,19 +24,6 @@ namespace blackbird {
 namespace M = rpc::methods;
 
 namespace {
-Error hip_err(hipError_t e, const char* what) {
-  return Error{ErrorCode::HIP_ERROR,
-               std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define BB_HIP(expr)                                  \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) {                           \
-      (void)hipGetLastError(); /* consume sticky */   \
-      return hip_err(_e, #expr);                      \
-    }                                                 \
-  } while (0)
-
 struct KeyMsg {
   std::string key;
   BB_FIELDS(key)
@@ -163,12 +151,12 @@ void GpuClient::release_staging_buf(void* p) {
 Result<void> GpuClient::init() {
   if (initialized_) return {};
   if (!gpu::available()) return Error{ErrorCode::NO_GPU, "no MI355X visible"};
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   for (auto& s : streams_)
-    BB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    BB_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   for (auto& s : fan_streams_)
-    BB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  BB_HIP(hipHostMalloc(&staging_, staging_size_, hipHostMallocDefault));
+    BB_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  BB_HIP_TRY(hipHostMalloc(&staging_, staging_size_, hipHostMallocDefault));
   initialized_ = true;
   return {};
 }
@@ -179,38 +167,26 @@ Result<void> GpuClient::init() {
 // is issued.
 uint8_t* GpuClient::resolve_pool_base(const PoolId& pool_id, AccessInfo* access,
                                       const AccessInfo* hint) {
-  bool is_dev = false;
-  int dev = -1;
-  uint64_t pool_size = 0;
-  if (void* base = LocalPools::inst().lookup(pool_id, &is_dev, &dev,
-                                             &pool_size)) {
-    if (is_dev) return static_cast<uint8_t*>(base);
-    // host pool in this process (pinned/shm tier): pin+map once so the GPU
-    // addresses it directly (PCIe DMA) instead of staging through a bounce
-    return static_cast<uint8_t*>(
-        c_.mapper_->host_dev_map(pool_id, base, pool_size));
+  PoolView v = PoolMapper::local(pool_id);
+  if (!v.base) {
+    // a pool of another process (one rank per GPU): IPC import or shm map.
+    // An unmapped tier of this process comes this way too, for its endpoint.
+    AccessInfo a;
+    if (hint && !hint->endpoint.empty()) {
+      a = *hint;
+    } else {
+      auto r = c_.pool_access(pool_id);
+      if (!r.ok()) return nullptr;
+      a = std::move(r.value());
+    }
+    v = c_.mapper_->remote(a);
+    if (access) *access = std::move(a);
   }
-  AccessInfo a;
-  if (hint && !hint->endpoint.empty()) {
-    a = *hint;
-  } else {
-    auto r = c_.pool_access(pool_id);
-    if (!r.ok()) return nullptr;
-    a = std::move(r.value());
-  }
-  uint8_t* out = nullptr;
-  if (a.kind == AccessKind::HIP_IPC && !a.ipc_handle_hex.empty()) {
-    // IPC pools come from other processes (one rank per GPU)
-    out = static_cast<uint8_t*>(
-        c_.mapper_->open_ipc(a.ipc_handle_hex, a.device_id));
-  } else if (a.kind == AccessKind::SHM && !a.shm_name.empty()) {
-    // host pool of ANOTHER process: shm-map it, then GPU-map the mapping
-    uint64_t sz = 0;
-    if (void* base = c_.mapper_->map_shm(a.shm_name, 0, &sz))
-      out = static_cast<uint8_t*>(c_.mapper_->host_dev_map(pool_id, base, sz));
-  }
-  if (access) *access = std::move(a);
-  return out;
+  if (!v.base || v.device) return v.base;
+  // host pool (pinned/shm tier), local or shm-mapped: pin+map once so the
+  // GPU addresses it directly (PCIe DMA) instead of staging through a bounce
+  return static_cast<uint8_t*>(
+      c_.mapper_->host_dev_map(pool_id, v.base, v.size));
 }
 
 uint8_t* GpuClient::resolve_device_ptr(const ShardPlacement& s) {
@@ -341,9 +317,9 @@ struct GpuClient::Router {
   // `si` rotating SDMA streams (checksum_batch and fused_put synchronize
   // their own streams internally)
   Result<void> sync() {
-    if (!copies.empty()) BB_HIP(hipStreamSynchronize(g.streams_[0]));
+    if (!copies.empty()) BB_HIP_TRY(hipStreamSynchronize(g.streams_[0]));
     for (int j = 0; j < std::min(si, kStreams); ++j)
-      BB_HIP(hipStreamSynchronize(g.streams_[j]));
+      BB_HIP_TRY(hipStreamSynchronize(g.streams_[j]));
     return {};
   }
 
@@ -356,8 +332,8 @@ struct GpuClient::Router {
       copies.push_back({src, dst, nbytes});
       return {};
     }
-    BB_HIP(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToDevice,
-                          g.streams_[si % kStreams]));
+    BB_HIP_TRY(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToDevice,
+                              g.streams_[si % kStreams]));
     ++si;
     return {};
   }
@@ -677,7 +653,7 @@ Result<uint64_t> GpuClient::get_device(const ObjectKey& key, void* dev_ptr,
   if (meta->size > capacity)
     return Error{ErrorCode::SIZE_MISMATCH, "device buffer too small"};
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
 
   Error last{ErrorCode::NO_PLACEMENT, "no copies"};
   for (const auto& copy : meta->copies) {
@@ -708,7 +684,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_range(
   std::vector<int32_t> statuses(items.size(), 0);
   if (items.empty()) return statuses;
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   KeysMsg req;
   for (const auto& it : items) req.keys.push_back(it.key);
   auto resp = c_.meta_call<KeysMsg, BatchGetWorkersResponse>(
@@ -767,7 +743,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_range(
   if (!descs.empty()) {
     BB_RETURN_IF_ERROR(gpu::batched_copy(
         descs.data(), static_cast<uint32_t>(descs.size()), streams_[0]));
-    BB_HIP(hipStreamSynchronize(streams_[0]));
+    BB_HIP_TRY(hipStreamSynchronize(streams_[0]));
   }
   return statuses;
 }
@@ -783,7 +759,7 @@ Result<void> GpuClient::patch_by_rewrite(const DevRangePatch& item,
   if (!range_inside(item.offset, item.length, info.size))
     return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + item.key};
   void* tmp = nullptr;
-  BB_HIP(hipMalloc(&tmp, std::max<uint64_t>(info.size, 16)));
+  BB_HIP_TRY(hipMalloc(&tmp, std::max<uint64_t>(info.size, 16)));
   auto run = [&]() -> Result<void> {
     auto got = get_device(item.key, tmp, info.size, /*verify=*/true);
     if (!got.ok()) return got.error();
@@ -810,7 +786,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
   std::vector<int32_t> statuses(items.size(), 0);
   if (items.empty()) return statuses;
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   std::vector<ObjectKey> keys;
   for (const auto& it : items) keys.push_back(it.key);
   auto started = c_.patch_start(keys);
@@ -1512,7 +1488,7 @@ Result<std::vector<int32_t>> GpuClient::batch_put_device_once(
     const std::vector<DevPutItem>& items, const PlacementConfig& cfg,
     BatchPutSession* sess) {
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   if (cfg.max_workers_per_copy <= 1)
     return batch_put_device_v2(items, cfg, sess);
 
@@ -1694,7 +1670,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device(
 Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
     const std::vector<DevGetItem>& items, bool verify, BatchGetSession* sess) {
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   {
     auto v2 = batch_get_device_v2(items, verify, sess);
     // a striped object in the batch makes the server signal fallback per
@@ -1771,7 +1747,7 @@ Result<std::vector<int32_t>> GpuClient::batch_get_device_once(
 Result<void> GpuClient::batch_shuffle_rccl(RcclEngine& comm,
                                            const std::vector<ShuffleWant>& want) {
   BB_RETURN_IF_ERROR(init());
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   RcclExchanger ex(comm, streams_[3]);
   GpuCopier cp(device_, streams_[4]);
   // serve keys out of this rank's visible pools: placement cache first

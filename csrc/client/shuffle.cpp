@@ -9,22 +9,13 @@
 #include "blackbird/common/log.h"
 #include "blackbird/common/serde.h"
 #include "blackbird/common/trace.h"
+#include "blackbird/gpu/hip_check.h"
 #include "blackbird/transport/rccl_engine.h"
 
 namespace blackbird {
 
 namespace {
 constexpr uint64_t kErrTotal = ~0ull;  // "my resolution failed" sentinel
-
-Error hip_err(hipError_t e, const char* what) {
-  return Error{ErrorCode::HIP_ERROR,
-               std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define BB_HIP(expr)                                  \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) return hip_err(_e, #expr);  \
-  } while (0)
 
 struct TransportBuf {  // RAII transport-memory allocation
   Copier& cp;
@@ -226,14 +217,14 @@ Result<void> RcclExchanger::alltoallv(const std::vector<const void*>& sp,
                                       const std::vector<void*>& rp,
                                       const std::vector<uint64_t>& rb) {
   BB_RETURN_IF_ERROR(e_.alltoallv(sp, sb, rp, rb, stream_));
-  BB_HIP(hipStreamSynchronize(stream_));
+  BB_HIP_TRY(hipStreamSynchronize(stream_));
   return {};
 }
 
 Result<void*> GpuCopier::alloc(uint64_t nbytes) {
-  BB_HIP(hipSetDevice(device_));
+  BB_HIP_TRY(hipSetDevice(device_));
   void* p = nullptr;
-  BB_HIP(hipMalloc(&p, nbytes));
+  BB_HIP_TRY(hipMalloc(&p, nbytes));
   return p;
 }
 
@@ -241,7 +232,7 @@ void GpuCopier::free(void* p) { (void)hipFree(p); }
 
 Result<void> GpuCopier::copy_batch(const gpu::CopyDesc* descs, uint32_t n) {
   BB_RETURN_IF_ERROR(gpu::batched_copy(descs, n, stream_));
-  BB_HIP(hipStreamSynchronize(stream_));
+  BB_HIP_TRY(hipStreamSynchronize(stream_));
   return {};
 }
 

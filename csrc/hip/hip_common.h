@@ -8,22 +8,9 @@
 #include <string>
 
 #include "blackbird/common/result.h"
+#include "blackbird/gpu/hip_check.h"
 
 namespace blackbird::gpu {
-
-inline Error hip_error(hipError_t e, const char* what) {
-  return Error{ErrorCode::HIP_ERROR,
-               std::string(what) + ": " + hipGetErrorString(e)};
-}
-
-#define BB_HIP_TRY(expr)                                        \
-  do {                                                          \
-    hipError_t _e = (expr);                                     \
-    if (_e != hipSuccess) {                                     \
-      (void)hipGetLastError(); /* consume sticky thread error */ \
-      return ::blackbird::gpu::hip_error(_e, #expr);            \
-    }                                                           \
-  } while (0)
 
 // Directly after a <<<>>> launch of the kernel `name` (a string literal).
 #define BB_HIP_LAUNCHED(name)                                     \

@@ -270,6 +270,9 @@ class GpuClient {
   void invalidate(const std::vector<ObjectKey>& keys);
   void clear_placement_cache() { cache_.clear(); }
 
+  // test hook: the device-visible base this client resolves a pool to
+  uint8_t* pool_base_for_test(const PoolId& id) { return resolve_pool_base(id); }
+
  private:
   // Resolve a shard to a device-visible pointer (local or IPC-mapped peer
   // HBM, GPU-mapped host tier); nullptr if the pool is not device-visible

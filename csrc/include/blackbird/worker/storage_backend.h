@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 
 #include "blackbird/allocation/pool_allocator.h"
@@ -85,6 +86,8 @@ class BackendBase : public StorageBackend {
  protected:
   Result<void> check_range(uint64_t offset, uint64_t len) const;
   void expire_reservations_locked(uint64_t now);
+  // a fresh token for [offset, +size), not yet in reservations_
+  ReservationToken new_token(uint64_t offset, uint64_t size);
 
   const uint64_t capacity_;
   const uint64_t reservation_ttl_ms_;
@@ -101,26 +104,25 @@ class BackendBase : public StorageBackend {
 // (hipIpcOpenMemHandle rejects same-process handles).
 class LocalPools {
  public:
+  struct Entry {
+    void* base;  // nullptr for an unmapped tier
+    uint64_t size;
+    bool is_device;
+    int device;
+    // same-process backend handle (valid while the pool is registered): lets
+    // clients embedded in the worker process reach UNMAPPED tiers (direct-IO
+    // NVMe) through the backend's read/write instead of TCP loopback
+    StorageBackend* backend;
+  };
+
   static LocalPools& inst();
   void add(const PoolId& id, void* base, uint64_t size, bool is_device,
            int device, StorageBackend* backend = nullptr);
   void remove(const PoolId& id);
-  // returns base or nullptr; *is_device/*device/*size set when found
-  void* lookup(const PoolId& id, bool* is_device = nullptr,
-               int* device = nullptr, uint64_t* size = nullptr);
-  // same-process backend handle (valid while the pool is registered): lets
-  // clients embedded in the worker process reach UNMAPPED tiers (direct-IO
-  // NVMe) through the backend's read/write instead of TCP loopback
-  StorageBackend* backend(const PoolId& id);
+  // the pool's entry as registered, read under one lock
+  std::optional<Entry> find(const PoolId& id);
 
  private:
-  struct Entry {
-    void* base;
-    uint64_t size;
-    bool is_device;
-    int device;
-    StorageBackend* backend;
-  };
   std::mutex mu_;
   std::map<PoolId, Entry> pools_;
 };

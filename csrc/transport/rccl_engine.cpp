@@ -8,6 +8,7 @@
 #include "blackbird/common/hex.h"
 #include "blackbird/common/types.h"
 #include "blackbird/common/log.h"
+#include "blackbird/gpu/hip_check.h"
 
 namespace blackbird {
 
@@ -20,13 +21,6 @@ Error rccl_err(ncclResult_t r, const char* what) {
   do {                                                  \
     ncclResult_t _r = (expr);                           \
     if (_r != ncclSuccess) return rccl_err(_r, #expr);  \
-  } while (0)
-#define BB_HIP(expr)                                                   \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess)                                              \
-      return Error{ErrorCode::HIP_ERROR,                               \
-                   std::string(#expr) + ": " + hipGetErrorString(_e)}; \
   } while (0)
 }  // namespace
 
@@ -47,7 +41,7 @@ Result<void> RcclEngine::init(std::shared_ptr<coord::CoordService> coord,
   rank_ = rank;
   nranks_ = nranks;
   device_ = device;
-  BB_HIP(hipSetDevice(device));
+  BB_HIP_TRY(hipSetDevice(device));
 
   const std::string key =
       "/blackbird/clusters/" + cluster_id + "/rccl/" + tag;
@@ -118,8 +112,9 @@ Result<void> RcclEngine::alltoallv(const std::vector<const void*>& send_ptrs,
   if (send_bytes[rank_] > 0) {
     if (send_bytes[rank_] != recv_bytes[rank_])
       return Error{ErrorCode::SIZE_MISMATCH, "self slot size mismatch"};
-    BB_HIP(hipMemcpyAsync(recv_ptrs[rank_], send_ptrs[rank_],
-                          send_bytes[rank_], hipMemcpyDeviceToDevice, stream));
+    BB_HIP_TRY(hipMemcpyAsync(recv_ptrs[rank_], send_ptrs[rank_],
+                              send_bytes[rank_], hipMemcpyDeviceToDevice,
+                              stream));
   }
   return {};
 }

@@ -27,14 +27,19 @@ void BackendBase::expire_reservations_locked(uint64_t now) {
   }
 }
 
+ReservationToken BackendBase::new_token(uint64_t offset, uint64_t size) {
+  ReservationToken t;
+  t.token_id = next_token_++;
+  t.offset = offset;
+  t.size = size;
+  t.expires_ms = now_ms() + reservation_ttl_ms_;
+  return t;
+}
+
 Result<ReservationToken> BackendBase::reserve(uint64_t size) {
   auto off = alloc_.allocate(size);
   if (!off.ok()) return off.error();
-  ReservationToken t;
-  t.token_id = next_token_++;
-  t.offset = off.value();
-  t.size = size;
-  t.expires_ms = now_ms() + reservation_ttl_ms_;
+  ReservationToken t = new_token(off.value(), size);
   std::lock_guard<std::mutex> g(mu_);
   expire_reservations_locked(now_ms());
   reservations_[t.token_id] = t;
@@ -44,11 +49,7 @@ Result<ReservationToken> BackendBase::reserve(uint64_t size) {
 Result<ReservationToken> BackendBase::reserve_at(uint64_t offset, uint64_t size) {
   BB_RETURN_IF_ERROR(check_range(offset, size));
   BB_RETURN_IF_ERROR(alloc_.reserve_exact(offset, size));
-  ReservationToken t;
-  t.token_id = next_token_++;
-  t.offset = offset;
-  t.size = size;
-  t.expires_ms = now_ms() + reservation_ttl_ms_;
+  ReservationToken t = new_token(offset, size);
   std::lock_guard<std::mutex> g(mu_);
   reservations_[t.token_id] = t;
   return t;
@@ -119,26 +120,16 @@ void LocalPools::add(const PoolId& id, void* base, uint64_t size,
   pools_[id] = Entry{base, size, is_device, device, backend};
 }
 
-StorageBackend* LocalPools::backend(const PoolId& id) {
-  std::lock_guard<std::mutex> g(mu_);
-  auto it = pools_.find(id);
-  return it == pools_.end() ? nullptr : it->second.backend;
-}
-
 void LocalPools::remove(const PoolId& id) {
   std::lock_guard<std::mutex> g(mu_);
   pools_.erase(id);
 }
 
-void* LocalPools::lookup(const PoolId& id, bool* is_device, int* device,
-                         uint64_t* size) {
+std::optional<LocalPools::Entry> LocalPools::find(const PoolId& id) {
   std::lock_guard<std::mutex> g(mu_);
   auto it = pools_.find(id);
-  if (it == pools_.end()) return nullptr;
-  if (is_device) *is_device = it->second.is_device;
-  if (device) *device = it->second.device;
-  if (size) *size = it->second.size;
-  return it->second.base;
+  if (it == pools_.end()) return std::nullopt;
+  return it->second;
 }
 
 }  // namespace blackbird

@@ -10,7 +10,8 @@
 //    process on the node; digests via the MFMA checksum kernel.
 //  * PinnedBackend (PINNED_CPU): shm + hipHostRegister — page-locked staging
 //    for the GPU→DRAM→NVMe spill path, still SHM-addressable by clients.
-//  * MmapDiskBackend (NVME/SSD/HDD): ftruncate+mmap(MAP_SHARED) backing file.
+//  * MmapDiskBackend (HDD): ftruncate+mmap(MAP_SHARED) backing file.
+// The host-mapped tiers share MappedBackend: one mapping and the IO over it.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -22,6 +23,7 @@
 #include "blackbird/common/hex.h"
 #include "blackbird/common/log.h"
 #include "blackbird/gpu/gpu_kernels.h"
+#include "blackbird/gpu/hip_check.h"
 #include "blackbird/worker/storage_backend.h"
 
 #include <hip/hip_runtime_api.h>
@@ -30,25 +32,86 @@ namespace blackbird {
 
 namespace {
 
-Error hip_err(hipError_t e, const char* what) {
-  return Error{ErrorCode::HIP_ERROR,
-               std::string(what) + ": " + hipGetErrorString(e)};
-}
+// ---------------------------------------------------- host-mapped tiers
+// One host mapping of capacity_ bytes and the bounds-checked IO over it. A
+// tier supplies how the mapping is made (map) and torn down (unmap), its
+// access_info() and its storage_class(); its destructor calls shutdown(),
+// which this class cannot do for it once the tier's part is destroyed.
+class MappedBackend : public BackendBase {
+ public:
+  using BackendBase::BackendBase;
 
-#define BB_HIP(expr)                                  \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) return hip_err(_e, #expr);  \
-  } while (0)
+  Result<void> initialize() final {
+    auto m = map();
+    if (!m.ok()) return m.error();
+    base_ = m.value();
+    return {};
+  }
+
+  void shutdown() final {
+    if (!base_) return;
+    unmap(base_);
+    base_ = nullptr;
+  }
+
+  void* base_ptr() const final { return base_; }
+
+  Result<void> write(uint64_t offset, const void* src, uint64_t len) final {
+    BB_RETURN_IF_ERROR(check_range(offset, len));
+    std::memcpy(static_cast<uint8_t*>(base_) + offset, src, len);
+    return {};
+  }
+  Result<void> read(uint64_t offset, void* dst, uint64_t len) final {
+    BB_RETURN_IF_ERROR(check_range(offset, len));
+    std::memcpy(dst, static_cast<uint8_t*>(base_) + offset, len);
+    return {};
+  }
+  Result<uint64_t> checksum(uint64_t offset, uint64_t len) final {
+    BB_RETURN_IF_ERROR(check_range(offset, len));
+    return gpu::checksum_cpu(static_cast<uint8_t*>(base_) + offset, len);
+  }
+
+ protected:
+  virtual Result<void*> map() = 0;
+  virtual void unmap(void* base) = 0;
+
+  // MAP_SHARED mapping of the whole pool over `fd`, which is closed either
+  // way; nullptr with errno set on failure
+  void* map_fd(int fd) const {
+    void* p = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    ::close(fd);
+    return p == MAP_FAILED ? nullptr : p;
+  }
+
+  // the advertisement of a mapping that other processes reach as `kind`
+  AccessInfo advertise(AccessKind kind) const {
+    AccessInfo a;
+    a.kind = kind;
+    a.base_addr = reinterpret_cast<uint64_t>(base_);
+    return a;
+  }
+
+ private:
+  void* base_ = nullptr;
+};
 
 // ------------------------------------------------------------- shm tier
-class ShmRamBackend : public BackendBase {
+class ShmRamBackend : public MappedBackend {
  public:
   ShmRamBackend(uint64_t cap, std::string shm_name, StorageClass cls)
-      : BackendBase(cap), shm_name_(std::move(shm_name)), class_(cls) {}
+      : MappedBackend(cap), shm_name_(std::move(shm_name)), class_(cls) {}
   ~ShmRamBackend() override { shutdown(); }
 
-  Result<void> initialize() override {
+  StorageClass storage_class() const override { return class_; }
+
+  AccessInfo access_info() const override {
+    AccessInfo a = advertise(AccessKind::SHM);
+    a.shm_name = shm_name_;
+    return a;
+  }
+
+ protected:
+  Result<void*> map() override {
     shm_unlink(shm_name_.c_str());
     int fd = shm_open(shm_name_.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
     if (fd < 0)
@@ -60,55 +123,23 @@ class ShmRamBackend : public BackendBase {
       return Error{ErrorCode::BACKEND_INIT_FAILED,
                    "ftruncate: " + std::string(strerror(errno))};
     }
-    base_ = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    ::close(fd);
-    if (base_ == MAP_FAILED) {
-      base_ = nullptr;
+    void* base = map_fd(fd);
+    if (!base) {
       shm_unlink(shm_name_.c_str());
       return Error{ErrorCode::BACKEND_INIT_FAILED,
                    "mmap: " + std::string(strerror(errno))};
     }
-    return {};
+    return base;
   }
 
-  void shutdown() override {
-    if (base_) {
-      munmap(base_, capacity_);
-      base_ = nullptr;
-      shm_unlink(shm_name_.c_str());
-    }
+  void unmap(void* base) override {
+    munmap(base, capacity_);
+    shm_unlink(shm_name_.c_str());
   }
 
-  StorageClass storage_class() const override { return class_; }
-  void* base_ptr() const override { return base_; }
-
-  AccessInfo access_info() const override {
-    AccessInfo a;
-    a.kind = AccessKind::SHM;
-    a.shm_name = shm_name_;
-    a.base_addr = reinterpret_cast<uint64_t>(base_);
-    return a;
-  }
-
-  Result<void> write(uint64_t offset, const void* src, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(static_cast<uint8_t*>(base_) + offset, src, len);
-    return {};
-  }
-  Result<void> read(uint64_t offset, void* dst, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(dst, static_cast<uint8_t*>(base_) + offset, len);
-    return {};
-  }
-  Result<uint64_t> checksum(uint64_t offset, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    return gpu::checksum_cpu(static_cast<uint8_t*>(base_) + offset, len);
-  }
-
- protected:
+ private:
   std::string shm_name_;
   StorageClass class_;
-  void* base_ = nullptr;
 };
 
 // ------------------------------------------------- pinned staging tier
@@ -118,96 +149,108 @@ class PinnedBackend : public ShmRamBackend {
       : ShmRamBackend(cap, std::move(shm_name), StorageClass::PINNED_CPU) {}
   ~PinnedBackend() override { shutdown(); }
 
-  Result<void> initialize() override {
-    BB_RETURN_IF_ERROR(ShmRamBackend::initialize());
-    if (gpu::available()) {
-      hipError_t e = hipHostRegister(base_, capacity_, hipHostRegisterDefault);
+ protected:
+  Result<void*> map() override {
+    auto base = ShmRamBackend::map();
+    if (base.ok() && gpu::available()) {
+      hipError_t e =
+          hipHostRegister(base.value(), capacity_, hipHostRegisterDefault);
       if (e == hipSuccess) registered_ = true;
       else BB_LOG(WARN) << "hipHostRegister failed (" << hipGetErrorString(e)
                         << ") — pinned tier degrades to pageable";
     }
-    return {};
+    return base;
   }
 
-  void shutdown() override {
-    if (registered_ && base_) {
-      (void)hipHostUnregister(base_);
+  void unmap(void* base) override {
+    if (registered_) {
+      (void)hipHostUnregister(base);
       registered_ = false;
     }
-    ShmRamBackend::shutdown();
+    ShmRamBackend::unmap(base);
   }
 
  private:
   bool registered_ = false;
 };
 
-
 // ------------------------------------------------------------ CXL.mem tier
 // DAX-device (or dax-mounted file) mapping; falls back to anonymous memory
 // when no device is present — the behavior the reference's CxlMemoryBackend
 // intended (cxl_memory_backend.cpp:73-121) but never shipped compiling (it
 // referenced error codes that did not exist).
-class CxlMemBackend : public BackendBase {
+class CxlMemBackend : public MappedBackend {
  public:
   CxlMemBackend(uint64_t cap, std::string dev_path)
-      : BackendBase(cap), path_(std::move(dev_path)) {}
+      : MappedBackend(cap), path_(std::move(dev_path)) {}
   ~CxlMemBackend() override { shutdown(); }
 
-  Result<void> initialize() override {
+  StorageClass storage_class() const override { return StorageClass::CXL_MEM; }
+  AccessInfo access_info() const override {
+    return advertise(AccessKind::TCP);  // DAX mappings are not name-shareable
+  }
+
+ protected:
+  Result<void*> map() override {
     if (!path_.empty()) {
       int fd = ::open(path_.c_str(), O_RDWR);
-      if (fd >= 0) {
-        base_ = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE, MAP_SHARED,
-                     fd, 0);
-        ::close(fd);
-        if (base_ != MAP_FAILED) return {};
-        base_ = nullptr;
-      }
+      if (fd >= 0)
+        if (void* base = map_fd(fd)) return base;
       BB_LOG(WARN) << "CXL_MEM: cannot map " << path_
                    << " — falling back to anonymous memory";
     }
-    base_ = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE,
-                 MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (base_ == MAP_FAILED) {
-      base_ = nullptr;
+    void* base = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE,
+                      MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (base == MAP_FAILED)
       return Error{ErrorCode::BACKEND_INIT_FAILED, "CXL_MEM mmap failed"};
-    }
-    return {};
+    return base;
   }
 
-  void shutdown() override {
-    if (base_) {
-      munmap(base_, capacity_);
-      base_ = nullptr;
-    }
-  }
+  void unmap(void* base) override { munmap(base, capacity_); }
 
-  StorageClass storage_class() const override { return StorageClass::CXL_MEM; }
-  void* base_ptr() const override { return base_; }
+ private:
+  std::string path_;
+};
+
+// ------------------------------------------------------------ disk tier
+class MmapDiskBackend : public MappedBackend {
+ public:
+  MmapDiskBackend(uint64_t cap, std::string path, StorageClass cls)
+      : MappedBackend(cap), path_(std::move(path)), class_(cls) {}
+  ~MmapDiskBackend() override { shutdown(); }
+
+  StorageClass storage_class() const override { return class_; }
   AccessInfo access_info() const override {
-    AccessInfo a;
-    a.kind = AccessKind::TCP;  // DAX mappings are not name-shareable
-    a.base_addr = reinterpret_cast<uint64_t>(base_);
-    return a;
+    return advertise(AccessKind::TCP);
   }
-  Result<void> write(uint64_t offset, const void* src, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(static_cast<uint8_t*>(base_) + offset, src, len);
-    return {};
+
+ protected:
+  Result<void*> map() override {
+    int fd = ::open(path_.c_str(), O_CREAT | O_RDWR, 0644);
+    if (fd < 0)
+      return Error{ErrorCode::BACKEND_INIT_FAILED,
+                   "open " + path_ + ": " + strerror(errno)};
+    if (ftruncate(fd, static_cast<off_t>(capacity_)) != 0) {
+      ::close(fd);
+      return Error{ErrorCode::BACKEND_INIT_FAILED,
+                   "ftruncate " + path_ + ": " + strerror(errno)};
+    }
+    void* base = map_fd(fd);
+    if (!base)
+      return Error{ErrorCode::BACKEND_INIT_FAILED,
+                   "mmap " + path_ + ": " + strerror(errno)};
+    madvise(base, capacity_, MADV_RANDOM);
+    return base;
   }
-  Result<void> read(uint64_t offset, void* dst, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(dst, static_cast<uint8_t*>(base_) + offset, len);
-    return {};
-  }
-  Result<uint64_t> checksum(uint64_t offset, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    return gpu::checksum_cpu(static_cast<uint8_t*>(base_) + offset, len);
+
+  void unmap(void* base) override {
+    msync(base, capacity_, MS_ASYNC);
+    munmap(base, capacity_);
   }
 
  private:
   std::string path_;
-  void* base_ = nullptr;
+  StorageClass class_;
 };
 
 // ------------------------------------------------------------ HBM tier
@@ -220,9 +263,9 @@ class HbmBackend : public BackendBase {
     if (!gpu::available())
       return Error{ErrorCode::NO_GPU,
                    "HBM tier requires an MI355X device (RAM_GPU pool)"};
-    BB_HIP(hipSetDevice(device_));
-    BB_HIP(hipMalloc(&base_, capacity_));
-    BB_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    BB_HIP_TRY(hipSetDevice(device_));
+    BB_HIP_TRY(hipMalloc(&base_, capacity_));
+    BB_HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     hipIpcMemHandle_t handle{};
     hipError_t e = hipIpcGetMemHandle(&handle, base_);
     if (e == hipSuccess) {
@@ -264,18 +307,18 @@ class HbmBackend : public BackendBase {
 
   Result<void> write(uint64_t offset, const void* src, uint64_t len) override {
     BB_RETURN_IF_ERROR(check_range(offset, len));
-    BB_HIP(hipSetDevice(device_));
-    BB_HIP(hipMemcpyAsync(static_cast<uint8_t*>(base_) + offset, src, len,
-                          hipMemcpyHostToDevice, stream_));
-    BB_HIP(hipStreamSynchronize(stream_));
+    BB_HIP_TRY(hipSetDevice(device_));
+    BB_HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(base_) + offset, src, len,
+                              hipMemcpyHostToDevice, stream_));
+    BB_HIP_TRY(hipStreamSynchronize(stream_));
     return {};
   }
   Result<void> read(uint64_t offset, void* dst, uint64_t len) override {
     BB_RETURN_IF_ERROR(check_range(offset, len));
-    BB_HIP(hipSetDevice(device_));
-    BB_HIP(hipMemcpyAsync(dst, static_cast<uint8_t*>(base_) + offset, len,
-                          hipMemcpyDeviceToHost, stream_));
-    BB_HIP(hipStreamSynchronize(stream_));
+    BB_HIP_TRY(hipSetDevice(device_));
+    BB_HIP_TRY(hipMemcpyAsync(dst, static_cast<uint8_t*>(base_) + offset, len,
+                              hipMemcpyDeviceToHost, stream_));
+    BB_HIP_TRY(hipStreamSynchronize(stream_));
     return {};
   }
   Result<uint64_t> checksum(uint64_t offset, uint64_t len) override {
@@ -289,73 +332,6 @@ class HbmBackend : public BackendBase {
   void* base_ = nullptr;
   hipStream_t stream_ = nullptr;
   std::string ipc_hex_;
-};
-
-// ------------------------------------------------------------ disk tier
-class MmapDiskBackend : public BackendBase {
- public:
-  MmapDiskBackend(uint64_t cap, std::string path, StorageClass cls)
-      : BackendBase(cap), path_(std::move(path)), class_(cls) {}
-  ~MmapDiskBackend() override { shutdown(); }
-
-  Result<void> initialize() override {
-    int fd = ::open(path_.c_str(), O_CREAT | O_RDWR, 0644);
-    if (fd < 0)
-      return Error{ErrorCode::BACKEND_INIT_FAILED,
-                   "open " + path_ + ": " + strerror(errno)};
-    if (ftruncate(fd, static_cast<off_t>(capacity_)) != 0) {
-      ::close(fd);
-      return Error{ErrorCode::BACKEND_INIT_FAILED,
-                   "ftruncate " + path_ + ": " + strerror(errno)};
-    }
-    base_ = mmap(nullptr, capacity_, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    ::close(fd);
-    if (base_ == MAP_FAILED) {
-      base_ = nullptr;
-      return Error{ErrorCode::BACKEND_INIT_FAILED,
-                   "mmap " + path_ + ": " + strerror(errno)};
-    }
-    madvise(base_, capacity_, MADV_RANDOM);
-    return {};
-  }
-
-  void shutdown() override {
-    if (base_) {
-      msync(base_, capacity_, MS_ASYNC);
-      munmap(base_, capacity_);
-      base_ = nullptr;
-    }
-  }
-
-  StorageClass storage_class() const override { return class_; }
-  void* base_ptr() const override { return base_; }
-
-  AccessInfo access_info() const override {
-    AccessInfo a;
-    a.kind = AccessKind::TCP;
-    a.base_addr = reinterpret_cast<uint64_t>(base_);
-    return a;
-  }
-
-  Result<void> write(uint64_t offset, const void* src, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(static_cast<uint8_t*>(base_) + offset, src, len);
-    return {};
-  }
-  Result<void> read(uint64_t offset, void* dst, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    std::memcpy(dst, static_cast<uint8_t*>(base_) + offset, len);
-    return {};
-  }
-  Result<uint64_t> checksum(uint64_t offset, uint64_t len) override {
-    BB_RETURN_IF_ERROR(check_range(offset, len));
-    return gpu::checksum_cpu(static_cast<uint8_t*>(base_) + offset, len);
-  }
-
- private:
-  std::string path_;
-  StorageClass class_;
-  void* base_ = nullptr;
 };
 
 }  // namespace
@@ -387,27 +363,23 @@ Result<std::unique_ptr<StorageBackend>> create_storage_backend(
     case StorageClass::RAM_GPU:
       b = std::make_unique<HbmBackend>(cfg.size_bytes, cfg.gpu_device_id);
       break;
-    case StorageClass::NVME:
-    case StorageClass::SSD: {
-      // async direct-IO tier (parity: the reference's io_uring backend used
-      // O_DIRECT for NVME/SSD)
-      if (cfg.mount_path.empty())
-        return Error{ErrorCode::CONFIG_INVALID, "disk pool needs mount_path"};
-      std::string path = cfg.mount_path + "/bb_" + worker_id + "_" +
-                         cfg.pool_id + ".dat";
-      b = make_direct_file_backend(cfg.size_bytes, path, cfg.storage_class);
-      break;
-    }
     case StorageClass::CXL_MEM:
       // mount_path = the DAX device/file; empty or unmappable → anonymous
       b = std::make_unique<CxlMemBackend>(cfg.size_bytes, cfg.mount_path);
       break;
+    case StorageClass::NVME:
+    case StorageClass::SSD:
     case StorageClass::HDD: {
       if (cfg.mount_path.empty())
         return Error{ErrorCode::CONFIG_INVALID, "disk pool needs mount_path"};
       std::string path = cfg.mount_path + "/bb_" + worker_id + "_" +
                          cfg.pool_id + ".dat";
-      b = std::make_unique<MmapDiskBackend>(cfg.size_bytes, path, cfg.storage_class);
+      if (cfg.storage_class == StorageClass::HDD)
+        b = std::make_unique<MmapDiskBackend>(cfg.size_bytes, path, cfg.storage_class);
+      else
+        // async direct-IO tier (parity: the reference's io_uring backend used
+        // O_DIRECT for NVME/SSD)
+        b = make_direct_file_backend(cfg.size_bytes, path, cfg.storage_class);
       break;
     }
   }

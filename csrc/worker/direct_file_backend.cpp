@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "blackbird/common/log.h"
+#include "blackbird/gpu/digest_spec.h"
 #include "blackbird/gpu/gpu_kernels.h"
 #include "blackbird/worker/storage_backend.h"
 
@@ -107,7 +108,7 @@ class DirectFileBackend : public BackendBase {
       uint64_t chunk = std::min<uint64_t>(kBounce, len - done);
       BB_RETURN_IF_ERROR(read(offset + done, buf.data(), chunk));
       h += gpu::checksum_cpu_tiles(buf.data(), chunk, tile);
-      tile += (chunk + 1023) / 1024;
+      tile += (chunk + digest::kTileBytes - 1) / digest::kTileBytes;
       done += chunk;
     }
     return gpu::checksum_cpu_finalize(h, len);
@@ -169,22 +170,10 @@ class DirectFileBackend : public BackendBase {
         op.len >= kAlign) {
       const uint64_t span = op.len / kAlign * kAlign;
       uint64_t done = 0;
-      while (done < span) {
-        ssize_t n = op.is_write
-                        ? pwrite(fd_, static_cast<uint8_t*>(op.buf) + done,
-                                 span - done, static_cast<off_t>(op.offset + done))
-                        : pread(fd_, static_cast<uint8_t*>(op.buf) + done,
-                                span - done, static_cast<off_t>(op.offset + done));
-        if (n < 0) {
-          if (errno == EINTR) continue;
-          if (errno == EINVAL) break;  // unaligned rejection: bounce it all
-          return Error{op.is_write ? ErrorCode::SEND_FAILED
-                                   : ErrorCode::RECV_FAILED,
-                       strerror(errno)};
-        }
-        if (n == 0) return Error{ErrorCode::RECV_FAILED, "eof"};
-        done += static_cast<uint64_t>(n);
-      }
+      int err = 0;
+      auto r = positional_io(op, span, done, &err);
+      // EINVAL is the unaligned rejection: bounce it all
+      if (!r.ok() && err != EINVAL) return r;
       if (done == op.len) return {};
       if (done == span && done > 0) {  // aligned body done: bounce the tail
         Op tail{op.is_write, op.offset + done,
@@ -230,14 +219,23 @@ class DirectFileBackend : public BackendBase {
 
   Result<void> plain_io(Op& op) {
     uint64_t done = 0;
-    while (done < op.len) {
+    return positional_io(op, op.len, done);
+  }
+
+  // pwrite/pread of op's first `len` bytes straight from or into its buffer,
+  // EINTR retried. `done` counts the bytes moved, also when it fails; the
+  // errno of a failed call goes to *err.
+  Result<void> positional_io(const Op& op, uint64_t len, uint64_t& done,
+                             int* err = nullptr) {
+    while (done < len) {
       ssize_t n = op.is_write
                       ? pwrite(fd_, static_cast<uint8_t*>(op.buf) + done,
-                               op.len - done, static_cast<off_t>(op.offset + done))
+                               len - done, static_cast<off_t>(op.offset + done))
                       : pread(fd_, static_cast<uint8_t*>(op.buf) + done,
-                              op.len - done, static_cast<off_t>(op.offset + done));
+                              len - done, static_cast<off_t>(op.offset + done));
       if (n < 0) {
         if (errno == EINTR) continue;
+        if (err) *err = errno;
         return Error{op.is_write ? ErrorCode::SEND_FAILED : ErrorCode::RECV_FAILED,
                      strerror(errno)};
       }

@@ -9,23 +9,12 @@
 #include "blackbird/common/trace.h"
 #include "blackbird/common/log.h"
 #include "blackbird/gpu/gpu_kernels.h"
+#include "blackbird/gpu/hip_check.h"
 #include "blackbird/rpc/messages.h"
 #include "blackbird/rpc/methods.h"
 #include "blackbird/rpc/rpc.h"
 
 namespace blackbird {
-
-namespace {
-Error hip_err(hipError_t e, const char* what) {
-  return Error{ErrorCode::HIP_ERROR,
-               std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define BB_HIP(expr)                                  \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) return hip_err(_e, #expr);  \
-  } while (0)
-}  // namespace
 
 TransferEngine::TransferEngine() : mapper_(std::make_shared<PoolMapper>()) {}
 
@@ -126,32 +115,12 @@ Result<void> TransferEngine::pull_one(StorageBackend& dst, uint64_t dst_offset,
 
   // resolve source to a pointer when one-sided access is possible; when the
   // mapping size is known, reject out-of-range source slices the same way
-  const uint8_t* src_ptr = nullptr;
-  bool src_is_gpu = false;
-  {
-    bool is_dev = false;
-    uint64_t src_pool_size = 0;  // 0 = unknown (IPC import)
-    if (void* base = LocalPools::inst().lookup(src.pool_id, &is_dev, nullptr,
-                                               &src_pool_size)) {
-      src_ptr = static_cast<const uint8_t*>(base) + src.offset;
-      src_is_gpu = is_dev;
-    } else if (src.access.kind == AccessKind::SHM && !src.access.shm_name.empty()) {
-      if (void* base =
-              mapper_->map_shm(src.access.shm_name, 0, &src_pool_size))
-        src_ptr = static_cast<const uint8_t*>(base) + src.offset;
-    } else if (src.access.kind == AccessKind::HIP_IPC &&
-               !src.access.ipc_handle_hex.empty() && gpu::available()) {
-      if (void* base =
-              mapper_->open_ipc(src.access.ipc_handle_hex, src.access.device_id)) {
-        src_ptr = static_cast<const uint8_t*>(base) + src.offset;
-        src_is_gpu = true;
-      }
-    }
-    if (src_ptr && src_pool_size > 0 &&
-        (src.length > src_pool_size ||
-         src.offset > src_pool_size - src.length))
-      return Error{ErrorCode::INVALID_OFFSET, "pull src range out of bounds"};
-  }
+  PoolView view = PoolMapper::local(src.pool_id);
+  if (!view.base) view = mapper_->remote(src.access);
+  if (view.base && !view.contains(src.offset, src.length))
+    return Error{ErrorCode::INVALID_OFFSET, "pull src range out of bounds"};
+  const uint8_t* src_ptr = view.base ? view.base + src.offset : nullptr;
+  const bool src_is_gpu = view.device;
 
   if (src_ptr && !dst_ptr) {
     // destination has no memory mapping (direct-IO file tier): move through
@@ -164,21 +133,21 @@ Result<void> TransferEngine::pull_one(StorageBackend& dst, uint64_t dst_offset,
                         static_cast<uint8_t*>(lane.pin) + kChunk};
     const uint64_t n_chunks = (src.length + kChunk - 1) / kChunk;
     uint64_t cur_len = std::min(src.length, kChunk);
-    BB_HIP(hipMemcpyAsync(half[0], src_ptr, cur_len, hipMemcpyDeviceToHost,
-                          stream));
-    BB_HIP(hipStreamSynchronize(stream));
+    BB_HIP_TRY(hipMemcpyAsync(half[0], src_ptr, cur_len,
+                              hipMemcpyDeviceToHost, stream));
+    BB_HIP_TRY(hipStreamSynchronize(stream));
     for (uint64_t c = 0; c < n_chunks; ++c) {
       const int cur = static_cast<int>(c & 1);
       uint64_t next_off = (c + 1) * kChunk;
       uint64_t next_len = 0;
       if (c + 1 < n_chunks) {
         next_len = std::min(src.length - next_off, kChunk);
-        BB_HIP(hipMemcpyAsync(half[1 - cur], src_ptr + next_off, next_len,
-                              hipMemcpyDeviceToHost, stream));
+        BB_HIP_TRY(hipMemcpyAsync(half[1 - cur], src_ptr + next_off, next_len,
+                                  hipMemcpyDeviceToHost, stream));
       }
       BB_RETURN_IF_ERROR(dst.write(dst_offset + c * kChunk, half[cur], cur_len));
       if (c + 1 < n_chunks) {
-        BB_HIP(hipStreamSynchronize(stream));
+        BB_HIP_TRY(hipStreamSynchronize(stream));
         cur_len = next_len;
       }
     }
@@ -197,8 +166,9 @@ Result<void> TransferEngine::pull_one(StorageBackend& dst, uint64_t dst_offset,
                              ? (dst_is_gpu ? hipMemcpyDeviceToDevice
                                            : hipMemcpyDeviceToHost)
                              : hipMemcpyHostToDevice;
-    BB_HIP(hipMemcpyAsync(dst_ptr + dst_offset, src_ptr, src.length, kind, stream));
-    BB_HIP(hipStreamSynchronize(stream));
+    BB_HIP_TRY(hipMemcpyAsync(dst_ptr + dst_offset, src_ptr, src.length, kind,
+                              stream));
+    BB_HIP_TRY(hipStreamSynchronize(stream));
     return {};
   }
 

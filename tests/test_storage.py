@@ -25,6 +25,8 @@ CLASSES = [
     (bb.StorageClass.PINNED_CPU, False),
     (bb.StorageClass.NVME, True),
     (bb.StorageClass.SSD, True),
+    (bb.StorageClass.HDD, True),
+    (bb.StorageClass.CXL_MEM, False),  # no DAX path: the anonymous fallback
 ]
 
 
