@@ -389,8 +389,8 @@ PYBIND11_MODULE(_core, m) {
   // Values travel as dicts so the tests can hand-build them; `msg` is one of
   // put_start2_req, put_start2_resp, get_workers2_req, get_workers2_resp,
   // upsert_start, commit_token, session_open, session_open_resp,
-  // commit_token_shards. Decoding a malformed body raises
-  // PROTOCOL_ERROR.
+  // commit_token_shards, patch_start_token, patch_start_token_resp. Decoding
+  // a malformed body raises PROTOCOL_ERROR.
   m.def("batch_wire_encode_for_test", [](const std::string& msg, py::dict v) {
     struct Item {
       std::string key;
@@ -458,6 +458,12 @@ PYBIND11_MODULE(_core, m) {
       out = wire::encode_commit_token_shards(
           v["token"].cast<uint64_t>(), v["release"].cast<bool>(), od.data(),
           od.size(), sd.data(), sd.size());
+    } else if (msg == "patch_start_token") {
+      out = wire::encode_patch_start_token(v["token"].cast<uint64_t>());
+    } else if (msg == "patch_start_token_resp") {
+      out = wire::encode_patch_start_token_response(
+          {v["obj_digests"].cast<std::vector<uint64_t>>(),
+           v["shard_digests"].cast<std::vector<uint64_t>>()});
     } else {
       throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
     }
@@ -529,6 +535,12 @@ PYBIND11_MODULE(_core, m) {
             v["release"] = (c.flags & 1) != 0;
             v["obj_digests"] = c.obj_digests;
             v["shard_digests"] = c.shard_digests;
+          } else if (msg == "patch_start_token") {
+            v["token"] = unwrap(wire::decode_patch_start_token(body));
+          } else if (msg == "patch_start_token_resp") {
+            auto r = unwrap(wire::decode_patch_start_token_response(body));
+            v["obj_digests"] = r.obj_digests;
+            v["shard_digests"] = r.shard_digests;
           } else {
             throw BlackbirdError(ErrorCode::INVALID_ARGUMENT, msg);
           }
@@ -782,6 +794,43 @@ PYBIND11_MODULE(_core, m) {
            }
            return out;
          }, py::arg("segs"), py::arg("obj_sizes"), py::arg("steps"),
+         py::arg("device") = 0, py::arg("before_step") = py::none());
+  // one FusedPatchPlan, replayed `steps` times: one (shard digests, object
+  // digests) pair per step, poisoned before each run. Step k's old digests
+  // are step k-1's outputs; the first step takes the given ones.
+  // before_step(k), when given, runs before replay k.
+  gm.def("fused_patch_plan",
+         [to_patch_segs](const PatchTuples& segs, const U64s& shard_lens,
+                         const U64s& obj_sizes, U64s shard_old, U64s obj_old,
+                         int steps, int device, py::object before_step) {
+           auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+           std::vector<std::pair<U64s, U64s>> out;
+           gpu::FusedPatchPlan plan;
+           {
+             py::gil_scoped_release rel;
+             unwrap_void(plan.build(ss.data(), static_cast<uint32_t>(ss.size()),
+                                    shard_lens.data(),
+                                    static_cast<uint32_t>(shard_lens.size()),
+                                    obj_sizes.data(),
+                                    static_cast<uint32_t>(obj_sizes.size()),
+                                    device));
+           }
+           for (int k = 0; k < steps; ++k) {
+             if (!before_step.is_none()) before_step(k);
+             out.emplace_back(U64s(shard_lens.size(), ~0ull),
+                              U64s(obj_sizes.size(), ~0ull));
+             {
+               py::gil_scoped_release rel;
+               unwrap_void(plan.run(shard_old.data(), obj_old.data(),
+                                    out.back().first.data(),
+                                    out.back().second.data()));
+             }
+             shard_old = out.back().first;
+             obj_old = out.back().second;
+           }
+           return out;
+         }, py::arg("segs"), py::arg("shard_lens"), py::arg("obj_sizes"),
+         py::arg("shard_old"), py::arg("obj_old"), py::arg("steps"),
          py::arg("device") = 0, py::arg("before_step") = py::none());
   gm.def("batched_copy",
          [](const std::vector<std::tuple<uint64_t, uint64_t, uint64_t>>& descs) {

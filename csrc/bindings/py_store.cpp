@@ -6,6 +6,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "blackbird/client/batch_wire.h"
 #include "blackbird/client/client.h"
 #include "blackbird/client/gpu_client.h"
 #include "blackbird/client/pool_mapper.h"
@@ -233,6 +234,12 @@ void bind_store(py::module_& m) {
          py::arg("release") = false)
       .def("upsert_start_token", [](KeystoneService& k, uint64_t token) {
         unwrap_void(k.upsert_start_token(token));
+      })
+      // (object checksums, shard digests in object, copy, shard order)
+      .def("patch_start_token", [](KeystoneService& k, uint64_t token) {
+        auto old = unwrap(k.patch_start_token(token));
+        return std::make_pair(std::move(old.obj_digests),
+                              std::move(old.shard_digests));
       })
       .def("commit_token", [](KeystoneService& k, uint64_t token,
                               const std::vector<uint64_t>& digests) {
@@ -469,6 +476,12 @@ void bind_store(py::module_& m) {
            }, py::arg("token"), py::arg("obj_digests"),
            py::arg("shard_digests"), py::arg("release") = false,
            py::call_guard<py::gil_scoped_release>())
+      // BATCH_PATCH_START_TOKEN: (object checksums, shard digests)
+      .def("patch_start_token", [](Client& c, uint64_t token) {
+        auto old = unwrap(c.patch_start_token(token));
+        return std::make_pair(std::move(old.obj_digests),
+                              std::move(old.shard_digests));
+      }, py::arg("token"), py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("host_session_steps",
                              &Client::host_session_steps)
       .def("batch_get", [](Client& c, const std::vector<std::string>& keys) {
@@ -516,6 +529,35 @@ void bind_store(py::module_& m) {
     std::vector<GpuClient::DevGetItem> items;
     GpuClient::BatchGetSession session;
   };
+  struct DevPatchBatch {
+    std::vector<GpuClient::DevRangePatch> items;
+    GpuClient::BatchPatchSession session;
+  };
+  using PatchItems =
+      std::vector<std::tuple<std::string, uint64_t, uint64_t, uint64_t>>;
+  auto to_patch_items = [](const PatchItems& items) {
+    std::vector<GpuClient::DevRangePatch> its;
+    for (auto& [k, off, p, n] : items)
+      its.push_back({k, off, reinterpret_cast<const void*>(p), n});
+    return its;
+  };
+  // active: the batch holds an established patch session. set_items swaps the
+  // item list under the session it holds (the next call then finds it bound
+  // to another list).
+  py::class_<DevPatchBatch>(m, "DevPatchBatch")
+      .def_property_readonly("size", [](const DevPatchBatch& b) { return b.items.size(); })
+      .def_property_readonly("active", [](const DevPatchBatch& b) {
+        return b.session.token != 0;
+      })
+      .def("set_items", [to_patch_items](DevPatchBatch& b, const PatchItems& items) {
+        b.items = to_patch_items(items);
+      }, py::arg("items"));
+  // items are (key, offset, dev_ptr, length), as for batch_patch_device
+  m.def("make_patch_batch", [to_patch_items](const PatchItems& items) {
+    DevPatchBatch b;
+    b.items = to_patch_items(items);
+    return b;
+  }, py::arg("items"));
   py::class_<DevPutBatch>(m, "DevPutBatch")
       .def_property_readonly("size", [](const DevPutBatch& b) { return b.items.size(); });
   py::class_<DevGetBatch>(m, "DevGetBatch")
@@ -630,6 +672,13 @@ void bind_store(py::module_& m) {
              py::gil_scoped_release rel;
              return unwrap(g.batch_patch_device(its));
            }, py::arg("items"))
+      // the same with the batch's patch session: the per-item statuses
+      .def("batch_patch_prepared", [](GpuClient& g, DevPatchBatch& b) {
+        py::gil_scoped_release rel;
+        return unwrap(g.batch_patch_device(b.items, &b.session));
+      }, py::arg("batch"))
+      .def_property_readonly("session_patch_steps",
+                             &GpuClient::session_patch_steps)
       .def("patch_device", [](GpuClient& g, const std::string& key,
                               uint64_t offset, uint64_t ptr, uint64_t length) {
         unwrap_void(g.patch_device(key, offset, reinterpret_cast<const void*>(ptr),

@@ -63,6 +63,20 @@ Result<void> decode_response(serde::Dec& d, size_t nitems, bool get,
 bool count_fits(uint32_t count, const serde::Dec& d) {
   return d.ok() && static_cast<uint64_t>(count) * 4 <= d.remaining();
 }
+
+// u32 n | u64*n: the list is sized only once the body is known to hold it
+void encode_u64_list(serde::Enc& e, const uint64_t* v, size_t n) {
+  e.num<uint32_t>(static_cast<uint32_t>(n));
+  for (size_t i = 0; i < n; ++i) e.num<uint64_t>(v[i]);
+}
+bool decode_u64_list(serde::Dec& d, std::vector<uint64_t>& out) {
+  const uint32_t n = d.num<uint32_t>();
+  if (!d.ok() || n > (1u << 24) || d.remaining() < n * sizeof(uint64_t))
+    return false;
+  out.resize(n);
+  for (auto& v : out) v = d.num<uint64_t>();
+  return true;
+}
 }  // namespace
 
 std::string encode_upsert_start(uint64_t token) {
@@ -141,11 +155,37 @@ std::string encode_commit_token_shards(uint64_t token, bool release,
   serde::Enc e;
   e.num<uint64_t>(token);
   e.num<uint8_t>(release ? 1 : 0);
-  e.num<uint32_t>(static_cast<uint32_t>(n));
-  for (size_t i = 0; i < n; ++i) e.num<uint64_t>(obj_digests[i]);
-  e.num<uint32_t>(static_cast<uint32_t>(m));
-  for (size_t i = 0; i < m; ++i) e.num<uint64_t>(shard_digests[i]);
+  encode_u64_list(e, obj_digests, n);
+  encode_u64_list(e, shard_digests, m);
   return std::move(e.buf);
+}
+
+std::string encode_patch_start_token(uint64_t token) {
+  return encode_upsert_start(token);  // both are one u64
+}
+
+Result<uint64_t> decode_patch_start_token(const std::string& body) {
+  serde::Dec d(body.data(), body.size());
+  const uint64_t token = d.num<uint64_t>();
+  if (!d.ok() || d.remaining() != 0) return bad("bad patch start request");
+  return token;
+}
+
+std::string encode_patch_start_token_response(const PatchStartDigests& r) {
+  serde::Enc e;
+  encode_u64_list(e, r.obj_digests.data(), r.obj_digests.size());
+  encode_u64_list(e, r.shard_digests.data(), r.shard_digests.size());
+  return std::move(e.buf);
+}
+
+Result<PatchStartDigests> decode_patch_start_token_response(
+    const std::string& body) {
+  serde::Dec d(body.data(), body.size());
+  PatchStartDigests r;
+  if (!decode_u64_list(d, r.obj_digests) ||
+      !decode_u64_list(d, r.shard_digests) || d.remaining() != 0)
+    return bad("bad patch start response");
+  return r;
 }
 
 Result<SessionOpen> decode_session_open(const std::string& body) {
@@ -176,16 +216,8 @@ Result<CommitTokenShards> decode_commit_token_shards(const std::string& body) {
   CommitTokenShards c;
   c.token = d.num<uint64_t>();
   c.flags = d.num<uint8_t>();
-  // each list is sized only once the body is known to hold it
-  auto list = [&d](std::vector<uint64_t>& out) {
-    const uint32_t n = d.num<uint32_t>();
-    if (!d.ok() || n > (1u << 24) || d.remaining() < n * sizeof(uint64_t))
-      return false;
-    out.resize(n);
-    for (auto& v : out) v = d.num<uint64_t>();
-    return true;
-  };
-  if (!list(c.obj_digests) || !list(c.shard_digests) || d.remaining() != 0)
+  if (!decode_u64_list(d, c.obj_digests) ||
+      !decode_u64_list(d, c.shard_digests) || d.remaining() != 0)
     return bad("bad shard commit request");
   return c;
 }

@@ -731,6 +731,13 @@ Result<uint64_t> Client::open_session(
   return wire::decode_session_open_response(r.value());
 }
 
+Result<wire::PatchStartDigests> Client::patch_start_token(uint64_t token) {
+  auto r = meta_call_raw(M::BATCH_PATCH_START_TOKEN,
+                         wire::encode_patch_start_token(token));
+  if (!r.ok()) return r.error();
+  return wire::decode_patch_start_token_response(r.value());
+}
+
 Result<void> Client::complete_by_keys(
     const std::vector<PutCompleteRequest>& reqs,
     const std::vector<uint32_t>& order, std::vector<int32_t>* statuses) {

@@ -93,6 +93,19 @@ ShardDigests shard_digests_of(const StripeRange& r,
   }
   return out;
 }
+// …or from each kernel object's shard count (a patch session's lists)…
+ShardDigests shard_digests_of(const StripeRange& r,
+                              const std::vector<uint32_t>& copy_shards,
+                              const std::vector<uint64_t>& shard_digests) {
+  ShardDigests out;
+  out.reserve(r.ncopies);
+  auto at = shard_digests.begin() + r.first_seg;
+  for (uint32_t c = 0; c < r.ncopies; ++c) {
+    out.emplace_back(at, at + copy_shards[r.first_obj + c]);
+    at += copy_shards[r.first_obj + c];
+  }
+  return out;
+}
 // …or from the launch's segment list: segs[k] of [r.first_seg, end) belongs
 // to copy segs[k].obj - r.first_obj.
 ShardDigests shard_digests_of(const StripeRange& r,
@@ -782,11 +795,12 @@ Result<void> GpuClient::patch_by_rewrite(const DevRangePatch& item,
 }
 
 Result<std::vector<int32_t>> GpuClient::batch_patch_device(
-    const std::vector<DevRangePatch>& items) {
+    const std::vector<DevRangePatch>& items, BatchPatchSession* sess) {
   std::vector<int32_t> statuses(items.size(), 0);
   if (items.empty()) return statuses;
   BB_RETURN_IF_ERROR(init());
   BB_HIP_TRY(hipSetDevice(device_));
+  if (auto fast = try_session_patch(items, sess)) return std::move(*fast);
   std::vector<ObjectKey> keys;
   for (const auto& it : items) keys.push_back(it.key);
   auto started = c_.patch_start(keys);
@@ -801,6 +815,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
   // counts shards (the digest lists), not the patched pieces.
   std::vector<gpu::PatchSeg> segs;
   std::vector<uint64_t> shard_lens, shard_old, obj_sizes, obj_old;
+  std::vector<uint32_t> copy_shards;  // per kernel object; a session keeps it
   std::vector<StripeRange> fused;
   std::vector<uint32_t> rewrite;  // item indices
   std::vector<GetWorkersResponse> rewrite_info(items.size());
@@ -851,6 +866,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
       }
       obj_sizes.push_back(info.size);
       obj_old.push_back(info.checksum);
+      copy_shards.push_back(static_cast<uint32_t>(copy.shards.size()));
       for (const auto& p : *pieces) {
         uint8_t* pool = resolve_device_ptr(copy.shards[p.shard]);
         const uint8_t* src =
@@ -870,6 +886,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
       shard_old.resize(shard_mark);
       obj_sizes.resize(obj_mark);
       obj_old.resize(obj_mark);
+      copy_shards.resize(obj_mark);
       aborts.push_back(it.key);
       rewrite_info[i] = info;
       rewrite.push_back(static_cast<uint32_t>(i));
@@ -909,11 +926,39 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
       order.push_back(f.item);
     }
     c_.cancel_puts(cancels);
+    // a session for the steps to come: the whole batch rode this launch and
+    // will commit. Opened before the commit, while PENDING pins the
+    // placements the run list points into.
+    if (sess) {
+      sess->end();
+      if (fused.size() == items.size() && reqs.size() == items.size()) {
+        std::vector<std::pair<ObjectKey, uint64_t>> objects;
+        objects.reserve(items.size());
+        for (const auto& f : fused)
+          objects.emplace_back(items[f.item].key, obj_sizes[f.first_obj]);
+        if (auto t = c_.open_session(objects, /*allow_striped=*/true);
+            t.ok() && t.value() != 0) {
+          sess->token = t.value();
+          sess->bound = items;
+          sess->segs = std::move(segs);
+          sess->shard_lens = std::move(shard_lens);
+          sess->obj_sizes = std::move(obj_sizes);
+          sess->copy_shards = std::move(copy_shards);
+          sess->ranges = std::move(fused);
+        }
+      }
+    }
     if (!reqs.empty()) {
       BB_RETURN_IF_ERROR(c_.complete_by_keys(reqs, order, &statuses));
       for (uint32_t i : order)
         if (statuses[i] == 0) ++patched_fused_items_;
+      // the first step commits by key: an item that did not leaves no session
+      if (sess)
+        for (uint32_t i : order)
+          if (statuses[i] != 0) sess->end();
     }
+  } else if (sess) {
+    sess->end();
   }
 
   for (uint32_t i : rewrite) {
@@ -930,41 +975,164 @@ Result<void> GpuClient::patch_device(const ObjectKey& key, uint64_t offset,
       batch_patch_device({DevRangePatch{key, offset, dev_ptr, length}}), key);
 }
 
+// A patch session's step: start by token, ONE launch (step_ladder), commit by
+// token. nullopt: nothing was flipped or written and the session is dropped —
+// the caller runs the full path, which may establish it again.
+std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_patch(
+    const std::vector<DevRangePatch>& items, BatchPatchSession* sess) {
+  if (!sess || sess->token == 0) return std::nullopt;
+  // the session is bound to one item list, field by field
+  bool same = sess->bound.size() == items.size();
+  for (size_t i = 0; same && i < items.size(); ++i) {
+    const auto& a = sess->bound[i];
+    const auto& b = items[i];
+    same = a.key == b.key && a.offset == b.offset && a.ptr == b.ptr &&
+           a.length == b.length;
+  }
+  if (!same) {
+    sess->end();
+    return std::nullopt;
+  }
+  BB_TRACE_SCOPE("bb::session_patch");
+  // RPC 1: the objects turn PENDING (placements pinned, epoch checked) and
+  // the answer is what the keystone records for them now
+  auto old = c_.patch_start_token(sess->token);
+  if (!old.ok()) {  // nothing flipped
+    sess->end();
+    return std::nullopt;
+  }
+  auto keys_of = [&](auto pred) {
+    std::vector<ObjectKey> keys;
+    for (size_t i = 0; i < items.size(); ++i)
+      if (pred(i)) keys.push_back(items[i].key);
+    return keys;
+  };
+  auto all = [](size_t) { return true; };
+  const uint32_t nshard = static_cast<uint32_t>(sess->shard_lens.size());
+  const uint32_t nobj = static_cast<uint32_t>(sess->obj_sizes.size());
+  if (old->obj_digests.size() != items.size() ||
+      old->shard_digests.size() != nshard) {
+    c_.patch_abort(keys_of(all));  // not what this session holds; unwritten
+    sess->end();
+    return std::nullopt;
+  }
+  // every copy is a kernel object of its own
+  std::vector<uint64_t> obj_old(nobj);
+  for (const auto& r : sess->ranges)
+    for (uint32_t c = 0; c < r.ncopies; ++c)
+      obj_old[r.first_obj + c] = old->obj_digests[r.item];
+  const std::vector<uint64_t>& shard_old = old->shard_digests;
+  // the patched keys leave the cache, as on the one-shot path
+  cache_.erase(key_list(
+      items, [](const DevRangePatch& it) -> const ObjectKey& { return it.key; }));
+
+  const gpu::PatchSeg* segs = sess->segs.data();
+  const uint32_t nseg = static_cast<uint32_t>(sess->segs.size());
+  const uint64_t* lens = sess->shard_lens.data();
+  const uint64_t* sizes = sess->obj_sizes.data();
+  std::vector<uint64_t> shard_new(nshard), obj_new(nobj);
+  auto launched = step_ladder(
+      sess->plan, sess->plan_failed, "patch ",
+      [&](auto& p) {
+        return p.build(segs, nseg, lens, nshard, sizes, nobj, device_);
+      },
+      [&](auto& p) {
+        return p.run(shard_old.data(), obj_old.data(), shard_new.data(),
+                     obj_new.data());
+      },
+      [&] {
+        return gpu::fused_patch(segs, nseg, lens, shard_old.data(), nshard,
+                                sizes, obj_old.data(), nobj, shard_new.data(),
+                                obj_new.data(), streams_[2]);
+      });
+  std::vector<int32_t> statuses(items.size(), 0);
+  auto torn = [&](ErrorCode code) {  // every key cancelled, the session over
+    c_.cancel_puts(keys_of(all));
+    statuses.assign(items.size(), static_cast<int32_t>(code));
+    sess->end();
+    return Result<std::vector<int32_t>>(std::move(statuses));
+  };
+  if (!launched.ok()) return {torn(launched.code())};
+
+  std::vector<uint64_t> per_item(items.size());
+  bool agree = true;
+  for (const auto& r : sess->ranges) {
+    per_item[r.item] = obj_new[r.first_obj];
+    if (!copies_agree(obj_new, r)) {
+      statuses[r.item] = static_cast<int32_t>(ErrorCode::CHECKSUM_MISMATCH);
+      agree = false;
+    }
+  }
+  if (!agree) {
+    // diverged replicas: their keys are cancelled, the others commit by key
+    std::vector<PutCompleteRequest> reqs;
+    std::vector<uint32_t> order;
+    for (const auto& r : sess->ranges) {
+      if (statuses[r.item] != 0) continue;
+      reqs.push_back(PutCompleteRequest{
+          items[r.item].key, per_item[r.item],
+          shard_digests_of(r, sess->copy_shards, shard_new)});
+      order.push_back(r.item);
+    }
+    c_.cancel_puts(keys_of([&](size_t i) { return statuses[i] != 0; }));
+    sess->end();
+    if (auto r = c_.complete_by_keys(reqs, order, &statuses); !r.ok())
+      return {r.error()};
+    for (uint32_t i : order)
+      if (statuses[i] == 0) ++patched_fused_items_;
+    return {Result<std::vector<int32_t>>(std::move(statuses))};
+  }
+  // RPC 2: shards lie in item, copy, shard order — the wire order
+  if (auto r = c_.commit_by_token_shards(sess->token, /*release=*/false,
+                                         per_item.data(), per_item.size(),
+                                         shard_new.data(), shard_new.size());
+      !r.ok())
+    return {torn(r.code())};
+  session_patch_steps_.fetch_add(1);
+  patched_fused_items_.fetch_add(items.size());
+  return {Result<std::vector<int32_t>>(std::move(statuses))};
+}
+
 // ------------------------ compact v2 batch protocol ------------------------
 // Pool-table responses with fixed-width placements: the client resolves each
 // POOL once (not each object) and decodes with zero per-item allocations.
 
+// The ladder of every session step: build the plan lazily, replay it, launch.
+template <typename Plan, typename Build, typename Replay, typename Launch>
+Result<void> GpuClient::step_ladder(std::shared_ptr<Plan>& plan,
+                                    bool& plan_failed, const char* what,
+                                    Build build, Replay replay, Launch launch) {
+  static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
+  if (!no_graph && !plan && !plan_failed) {
+    auto built = std::make_shared<Plan>();
+    auto rb = build(*built);
+    if (rb.ok()) {
+      plan = std::move(built);
+    } else {
+      plan_failed = true;       // capture unsupported: launch path
+      (void)hipGetLastError();  // clear any sticky launch error
+      BB_LOG(WARN) << what << "session graph capture unavailable ("
+                   << rb.error().message << "); using per-op launches";
+    }
+  }
+  if (plan) {
+    auto r = replay(*plan);
+    if (r.ok()) {
+      session_graph_steps_.fetch_add(1);
+      return r;
+    }
+    plan.reset();  // replay failed: fall through to launches
+    plan_failed = true;
+  }
+  return launch();
+}
+
 // The launch of one session step, put or get, plain or striped.
 Result<GpuClient::StepDigests> GpuClient::session_step(SessionCore& sess,
                                                        bool put) {
-  static const bool no_graph = std::getenv("BB_NO_HIPGRAPH") != nullptr;
-  // the ladder of either form: build the plan lazily, replay it, launch
-  auto run = [&](auto& plan, auto build, auto replay,
-                 auto launch) -> Result<void> {
-    using Plan = typename std::decay_t<decltype(plan)>::element_type;
-    if (!no_graph && !plan && !sess.plan_failed) {
-      auto built = std::make_shared<Plan>();
-      auto rb = build(*built);
-      if (rb.ok()) {
-        plan = std::move(built);
-      } else {
-        sess.plan_failed = true;  // capture unsupported: launch path
-        (void)hipGetLastError();   // clear any sticky launch error
-        BB_LOG(WARN) << (sess.striped() ? "striped " : "")
-                     << "session graph capture unavailable ("
-                     << rb.error().message << "); using per-op launches";
-      }
-    }
-    if (plan) {
-      auto r = replay(*plan);
-      if (r.ok()) {
-        session_graph_steps_.fetch_add(1);
-        return r;
-      }
-      plan.reset();  // replay failed: fall through to launches
-      sess.plan_failed = true;
-    }
-    return launch();
+  auto run = [&](auto& plan, auto build, auto replay, auto launch) {
+    return step_ladder(plan, sess.plan_failed, sess.striped() ? "striped " : "",
+                       build, replay, launch);
   };
   StepDigests d;
   Result<void> r{};

@@ -125,10 +125,11 @@ Result<void> enqueue_digest(void* device_block, uint32_t n, uint64_t total_tiles
   return {};
 }
 
-// A step captured once and replayed: what FusedPutPlan and FusedStripePlan
-// own and how they capture. The step's descriptors live in a device block
-// uploaded once; its digests land in a pinned buffer; capture and replay
-// happen on a dedicated non-blocking stream.
+// A step captured once and replayed: what FusedPutPlan, FusedStripePlan and
+// FusedPatchPlan (patch.hip) own and how they capture. The step's descriptors
+// live in a device block uploaded once; its digests land in a pinned buffer
+// (which FusedPatchPlan also uploads a step's old digests from); capture and
+// replay happen on a dedicated non-blocking stream.
 struct GraphStep {
   hipStream_t stream = nullptr;   // dedicated capture/replay stream
   hipGraphExec_t exec = nullptr;

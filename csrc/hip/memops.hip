@@ -176,6 +176,23 @@ struct XferPool {
 XferPool g_xfer;
 }  // namespace
 
+namespace {
+constexpr int kMaxDevices = 64;
+std::mutex g_anchor_mu;
+hipStream_t g_anchor[kMaxDevices] = {};
+}  // namespace
+
+Result<hipStream_t> staging_anchor() {
+  int dev = 0;
+  BB_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxDevices)
+    return Error{ErrorCode::INVALID_ARGUMENT, "device index out of range"};
+  std::lock_guard<std::mutex> g(g_anchor_mu);
+  if (!g_anchor[dev])
+    BB_HIP_TRY(hipStreamCreateWithFlags(&g_anchor[dev], hipStreamNonBlocking));
+  return g_anchor[dev];
+}
+
 Result<void> acquire_xfer_stream(XferStream& out) {
   BB_HIP_TRY(g_xfer.ensure());
   const uint32_t i = g_xfer.next.fetch_add(1) % kXferStreams;

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <vector>
+#include <memory>
 
 #include "batch_launch.hip.h"
 #include "blackbird/gpu/gpu_kernels.h"
@@ -22,26 +22,31 @@ using namespace blackbird::gpu::dev;
 
 namespace {
 
-// {segs[nseg] | prefix[nseg] | lens[nshard + nobj] | acc[nshard + nobj]} in
-// one allocation, same offsets in the pinned host image and on the device.
-// lens = {shard_lens | obj_sizes}; acc = {shard_acc | obj_acc}, seeded by the
-// host with unfinalize(old digest, length). All of it is uploaded in one
-// copy; acc is finalized in place and read back as one range.
+// {segs[nseg] | prefix[nseg] | lens[n] | old[n] | acc[n]}, n = nshard + nobj,
+// in one allocation, same offsets in the pinned host image and on the
+// device. lens = {shard_lens | obj_sizes}; old = the recorded digests, as
+// recorded, {shard | object}; acc = the wrapped sums of term(new) - term(old)
+// of the patched tiles, zeroed on the device, finalized in place over old and
+// read back as one range. {segs | prefix | lens} is all a plan needs to keep;
+// old changes every step.
 struct PatchBlock {
   uint32_t nseg, nshard, nobj;
 
   uint32_t nacc() const { return nshard + nobj; }
   size_t out_bytes() const { return size_t{nacc()} * sizeof(uint64_t); }
-  size_t bytes() const {
-    return nseg * (sizeof(PatchSeg) + sizeof(uint64_t)) + 2 * out_bytes();
+  size_t fixed_bytes() const {  // {segs | prefix | lens}
+    return nseg * (sizeof(PatchSeg) + sizeof(uint64_t)) + out_bytes();
   }
+  size_t upload_bytes() const { return fixed_bytes() + out_bytes(); }  // + old
+  size_t bytes() const { return upload_bytes() + out_bytes(); }
 
   PatchSeg* segs(void* base) const { return static_cast<PatchSeg*>(base); }
   uint64_t* prefix(void* base) const {
     return reinterpret_cast<uint64_t*>(segs(base) + nseg);
   }
   uint64_t* lens(void* base) const { return prefix(base) + nseg; }
-  uint64_t* acc(void* base) const { return lens(base) + nacc(); }
+  uint64_t* old(void* base) const { return lens(base) + nacc(); }
+  uint64_t* acc(void* base) const { return old(base) + nacc(); }
 };
 static_assert(sizeof(PatchSeg) % sizeof(uint64_t) == 0);
 
@@ -54,12 +59,52 @@ fused_patch_kernel(const PatchSeg* __restrict__ segs,
                           obj_acc);
 }
 
-// Each sum finalized with the length its digest is taken over.
+// Each delta added to the sum its old digest was finalized from, and the
+// result finalized with the same length: a delta of 0 gives the old digest
+// back bit for bit.
 __global__ void fused_patch_finalize_kernel(const uint64_t* __restrict__ lens,
+                                            const uint64_t* __restrict__ old,
                                             uint32_t n,
                                             unsigned long long* __restrict__ acc) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] = digest::finalize(acc[i], lens[i]);
+  if (i < n)
+    acc[i] = digest::finalize(digest::unfinalize(old[i], lens[i]) + acc[i],
+                              lens[i]);
+}
+
+// The host image of {segs | prefix | lens}. Returns the total tile count.
+uint64_t fill_patch_block(const PatchBlock& b, void* host, const PatchSeg* segs,
+                          const uint64_t* shard_lens,
+                          const uint64_t* obj_sizes) {
+  if (b.nseg) std::memcpy(b.segs(host), segs, b.nseg * sizeof(PatchSeg));
+  uint64_t* lens = b.lens(host);
+  if (b.nshard) std::memcpy(lens, shard_lens, b.nshard * sizeof(uint64_t));
+  if (b.nobj) std::memcpy(lens + b.nshard, obj_sizes, b.nobj * sizeof(uint64_t));
+  return fill_prefix(segs, b.nseg, digest::kTileBytes, b.prefix(host));
+}
+
+// The patch step over an uploaded block whose old digests are in place: zero
+// the accumulators -> patch and hash every tile -> finalize over the old
+// digests -> the new digests, {shard | object}, to host_out (pinned). Only
+// enqueues; the caller synchronizes or captures `stream` (the twin of
+// enqueue_stripe).
+Result<void> enqueue_patch(void* device_block, const PatchBlock& b,
+                           uint64_t total_tiles, uint64_t* host_out,
+                           hipStream_t stream) {
+  auto* d_acc = reinterpret_cast<unsigned long long*>(b.acc(device_block));
+  BB_HIP_TRY(hipMemsetAsync(d_acc, 0, b.out_bytes(), stream));
+  if (total_tiles > 0) {
+    fused_patch_kernel<<<digest_grid(total_tiles), kBlock, 0, stream>>>(
+        b.segs(device_block), b.prefix(device_block), b.nseg, total_tiles,
+        d_acc, d_acc + b.nshard);
+    BB_HIP_LAUNCHED("fused_patch_kernel");
+  }
+  fused_patch_finalize_kernel<<<(b.nacc() + 255) / 256, 256, 0, stream>>>(
+      b.lens(device_block), b.old(device_block), b.nacc(), d_acc);
+  BB_HIP_LAUNCHED("fused_patch_finalize_kernel");
+  BB_HIP_TRY(hipMemcpyAsync(host_out, d_acc, b.out_bytes(),
+                            hipMemcpyDeviceToHost, stream));
+  return {};
 }
 
 thread_local DescStaging g_patch_stage;
@@ -77,9 +122,8 @@ Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
   BB_RETURN_IF_ERROR(check_patch_segs(segs, nseg, shard_lens, shard_old, nshard,
                                       obj_sizes, obj_old, nobj));
   // before any HIP call: a launch without a tile needs no device
-  std::vector<uint64_t> prefix(nseg);
-  const uint64_t total =
-      fill_prefix(segs, nseg, digest::kTileBytes, prefix.data());
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < nseg; ++i) total += tile_count(segs[i].nbytes);
   if (total == 0) {  // nothing patched: every digest stands
     if (nshard) std::memcpy(out_shard_digests, shard_old, nshard * sizeof(uint64_t));
     if (nobj) std::memcpy(out_obj_digests, obj_old, nobj * sizeof(uint64_t));
@@ -95,32 +139,71 @@ Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
   void* host = g_patch_stage.pinned;
   void* dev = g_patch_stage.device;
 
-  std::memcpy(b.segs(host), segs, nseg * sizeof(PatchSeg));
-  std::memcpy(b.prefix(host), prefix.data(), nseg * sizeof(uint64_t));
-  uint64_t* h_lens = b.lens(host);
-  uint64_t* h_acc = b.acc(host);
-  for (uint32_t i = 0; i < nshard; ++i) {
-    h_lens[i] = shard_lens[i];
-    h_acc[i] = digest::unfinalize(shard_old[i], shard_lens[i]);
-  }
-  for (uint32_t i = 0; i < nobj; ++i) {
-    h_lens[nshard + i] = obj_sizes[i];
-    h_acc[nshard + i] = digest::unfinalize(obj_old[i], obj_sizes[i]);
-  }
-  BB_HIP_TRY(hipMemcpyAsync(dev, host, b.bytes(), hipMemcpyHostToDevice, stream));
-
-  auto* d_acc = reinterpret_cast<unsigned long long*>(b.acc(dev));
-  fused_patch_kernel<<<digest_grid(total), kBlock, 0, stream>>>(
-      b.segs(dev), b.prefix(dev), nseg, total, d_acc, d_acc + nshard);
-  BB_HIP_LAUNCHED("fused_patch_kernel");
-  fused_patch_finalize_kernel<<<(b.nacc() + 255) / 256, 256, 0, stream>>>(
-      b.lens(dev), b.nacc(), d_acc);
-  BB_HIP_LAUNCHED("fused_patch_finalize_kernel");
-  BB_HIP_TRY(hipMemcpyAsync(h_acc, d_acc, b.out_bytes(), hipMemcpyDeviceToHost,
+  fill_patch_block(b, host, segs, shard_lens, obj_sizes);
+  uint64_t* h_old = b.old(host);
+  if (nshard) std::memcpy(h_old, shard_old, nshard * sizeof(uint64_t));
+  if (nobj) std::memcpy(h_old + nshard, obj_old, nobj * sizeof(uint64_t));
+  BB_HIP_TRY(hipMemcpyAsync(dev, host, b.upload_bytes(), hipMemcpyHostToDevice,
                             stream));
+  uint64_t* h_out = b.acc(host);
+  BB_RETURN_IF_ERROR(enqueue_patch(dev, b, total, h_out, stream));
   BB_HIP_TRY(hipStreamSynchronize(stream));
-  if (nshard) std::memcpy(out_shard_digests, h_acc, nshard * sizeof(uint64_t));
-  if (nobj) std::memcpy(out_obj_digests, h_acc + nshard, nobj * sizeof(uint64_t));
+  if (nshard) std::memcpy(out_shard_digests, h_out, nshard * sizeof(uint64_t));
+  if (nobj) std::memcpy(out_obj_digests, h_out + nshard, nobj * sizeof(uint64_t));
+  return {};
+}
+
+// ---------------- hipGraph-replayed patch session step (FusedPatchPlan) ----
+// The patch counterpart of FusedStripePlan: {segs | prefix | lens} is uploaded
+// once; what changes every step, the old digests, rides the captured chain as
+// its first node, a copy from the plan's pinned zone, which the last node
+// fills with the new digests.
+
+struct FusedPatchPlan::Impl : GraphStep {};
+
+FusedPatchPlan::~FusedPatchPlan() { delete impl_; }
+
+Result<void> FusedPatchPlan::build(const PatchSeg* segs, uint32_t nseg,
+                                   const uint64_t* shard_lens, uint32_t nshard,
+                                   const uint64_t* obj_sizes, uint32_t nobj,
+                                   int device) {
+  if (impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan already built"};
+  if (nseg == 0) return Error{ErrorCode::INVALID_ARGUMENT, "empty run list"};
+  BB_RETURN_IF_ERROR(
+      check_patch_geometry(segs, nseg, shard_lens, nshard, obj_sizes, nobj));
+  const PatchBlock b{nseg, nshard, nobj};
+  auto h_block = std::make_unique<unsigned char[]>(b.fixed_bytes());
+  const uint64_t total =
+      fill_patch_block(b, h_block.get(), segs, shard_lens, obj_sizes);
+  if (total == 0) return Error{ErrorCode::INVALID_ARGUMENT, "zero-byte batch"};
+
+  BB_HIP_TRY(hipSetDevice(device));
+  auto impl = std::make_unique<Impl>();
+  BB_RETURN_IF_ERROR(impl->prepare(h_block.get(), b.fixed_bytes(), b.bytes(),
+                                   b.out_bytes()));
+  BB_RETURN_IF_ERROR(impl->capture([&](hipStream_t s) -> Result<void> {
+    BB_HIP_TRY(hipMemcpyAsync(b.old(impl->dev), impl->h_out, b.out_bytes(),
+                              hipMemcpyHostToDevice, s));
+    return enqueue_patch(impl->dev, b, total, impl->h_out, s);
+  }));
+  nshard_ = nshard;
+  nobj_ = nobj;
+  impl_ = impl.release();
+  return {};
+}
+
+Result<void> FusedPatchPlan::run(const uint64_t* shard_old,
+                                 const uint64_t* obj_old,
+                                 uint64_t* out_shard_digests,
+                                 uint64_t* out_obj_digests) {
+  if (!impl_) return Error{ErrorCode::INVALID_ARGUMENT, "plan not built"};
+  BB_RETURN_IF_ERROR(check_patch_digests(shard_old, nshard_, obj_old, nobj_));
+  uint64_t* zone = impl_->h_out;
+  if (nshard_) std::memcpy(zone, shard_old, nshard_ * sizeof(uint64_t));
+  if (nobj_) std::memcpy(zone + nshard_, obj_old, nobj_ * sizeof(uint64_t));
+  BB_RETURN_IF_ERROR(impl_->replay());
+  if (nshard_) std::memcpy(out_shard_digests, zone, nshard_ * sizeof(uint64_t));
+  if (nobj_) std::memcpy(out_obj_digests, zone + nshard_, nobj_ * sizeof(uint64_t));
   return {};
 }
 

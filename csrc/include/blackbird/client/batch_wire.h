@@ -1,7 +1,8 @@
 // Wire codec of the compact v2 batch protocol: BATCH_PUT_START2,
 // BATCH_GET_WORKERS2, BATCH_UPSERT_START and BATCH_COMMIT_TOKEN, and of the
 // two session messages that serve striped copies, BATCH_SESSION_OPEN and
-// BATCH_COMMIT_TOKEN_SHARDS. Clients and the keystone handlers both go
+// BATCH_COMMIT_TOKEN_SHARDS, and of the patch session's start,
+// BATCH_PATCH_START_TOKEN. Clients and the keystone handlers both go
 // through these functions; nothing else spells the layouts out.
 //
 //   BATCH_PUT_START2 request
@@ -26,6 +27,12 @@
 //   BATCH_COMMIT_TOKEN_SHARDS
 //     u64 token | u8 flags (bit 0: release) | u32 n | u64*n | u32 m | u64*m
 //     (n object digests; m shard digests in object, copy, shard order)
+//   BATCH_PATCH_START_TOKEN request
+//     u64 token
+//   BATCH_PATCH_START_TOKEN response
+//     u32 n | u64*n | u32 m | u64*m
+//     (the recorded digests, in the order BATCH_COMMIT_TOKEN_SHARDS takes the
+//     new ones: n object checksums; m shard digests)
 //   pool table           u16 npools | str pool_id * npools
 //
 // The responses carry no item count (the caller knows how many it asked for).
@@ -96,6 +103,12 @@ struct CommitTokenShards {
   std::vector<uint64_t> shard_digests;  // object, copy, shard order
 };
 
+// What the keystone holds for a patch session's objects when a step starts.
+struct PatchStartDigests {
+  std::vector<uint64_t> obj_digests;
+  std::vector<uint64_t> shard_digests;  // object, copy, shard order
+};
+
 // ---- requests (clients encode; items are keys or structs with .key/.size)
 template <typename T>
 const ObjectKey& key_of(const T& item) {
@@ -153,6 +166,8 @@ std::string encode_session_open_response(uint64_t token);
 std::string encode_commit_token_shards(uint64_t token, bool release,
                                        const uint64_t* obj_digests, size_t n,
                                        const uint64_t* shard_digests, size_t m);
+std::string encode_patch_start_token(uint64_t token);
+std::string encode_patch_start_token_response(const PatchStartDigests& r);
 
 // ---- requests (keystone decodes); PROTOCOL_ERROR on a malformed body
 Result<PutStart2Request> decode_put_start2_request(const std::string& body);
@@ -163,6 +178,9 @@ Result<CommitToken> decode_commit_token(const std::string& body);
 Result<SessionOpen> decode_session_open(const std::string& body);
 Result<uint64_t> decode_session_open_response(const std::string& body);
 Result<CommitTokenShards> decode_commit_token_shards(const std::string& body);
+Result<uint64_t> decode_patch_start_token(const std::string& body);
+Result<PatchStartDigests> decode_patch_start_token_response(
+    const std::string& body);
 
 // ---- responses
 // Pool table under construction: interns pool ids in first-seen order.

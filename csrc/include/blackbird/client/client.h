@@ -28,6 +28,10 @@
 
 namespace blackbird {
 
+namespace wire {
+struct PatchStartDigests;  // batch_wire.h
+}
+
 struct ClientOptions {
   std::string keystone_endpoint = "127.0.0.1:9090";
   // Service discovery: when set (and keystone_endpoint is empty), the
@@ -165,6 +169,11 @@ class Client {
   Result<void> commit_by_token_shards(uint64_t token, bool release,
                                       const uint64_t* obj_digests, size_t n,
                                       const uint64_t* shard_digests, size_t m);
+  // BATCH_PATCH_START_TOKEN: a patch step of a session opened while a
+  // patch_start held its objects PENDING. The objects turn PENDING again and
+  // the answer is what the keystone records for them now, in the order of
+  // commit_by_token_shards, the step's commit. Any error: nothing changed.
+  Result<wire::PatchStartDigests> patch_start_token(uint64_t token);
   // steps served by the host session fast path (tests/bench introspection)
   uint64_t host_session_steps() const { return host_session_steps_.load(); }
 

@@ -205,15 +205,54 @@ class GpuClient {
   // (verified) into a temporary device buffer, the range overlaid and the
   // object put back with replace=true; right on every tier and placement.
   // The patched keys leave this client's placement cache, which also ends
-  // every session bound to them; other clients' cached verified gets
-  // mismatch and fall back to the RPC path.
+  // every put and get session bound to them; other clients' cached verified
+  // gets mismatch and fall back to the RPC path.
+  //
+  // Patch sessions: a caller that patches the SAME item list (keys, offsets,
+  // buffers, lengths, order) every step passes a session object. The first
+  // call runs the path above and, if every item rode the fused launch and
+  // every replica agreed, opens a server session (BATCH_SESSION_OPEN, while
+  // the patch start's PENDING pins the placements) before it commits by key;
+  // the session keeps the launch's run list. Every later call costs one
+  // BATCH_PATCH_START_TOKEN (8 bytes out; the recorded digests back, flat —
+  // the server's, so that another writer's re-put in place is subtracted
+  // right), one replay of a captured gpu::FusedPatchPlan (session_step's
+  // ladder: launches under BB_NO_HIPGRAPH or after a failed capture or
+  // replay) and one BATCH_COMMIT_TOKEN_SHARDS. A start that is refused has
+  // flipped nothing: the session is dropped and the same call runs the full
+  // path, which may establish it again. Past the start the bytes are being
+  // written: a failed launch or commit cancels every key and ends the
+  // session; a replica that disagrees is CHECKSUM_MISMATCH and cancelled,
+  // the others commit by key, and the session ends. The session holds no
+  // placement-cache binding: the server's epoch check at every start is what
+  // guards the pool addresses it keeps.
+  struct BatchPatchSession {
+    uint64_t token = 0;  // server session token (0 = not established)
+    std::vector<DevRangePatch> bound;  // the item list the lists below serve
+    // the fused_patch argument lists but for the old digests
+    std::vector<gpu::PatchSeg> segs;
+    std::vector<uint64_t> shard_lens, obj_sizes;
+    std::vector<uint32_t> copy_shards;  // shards of each kernel object
+    std::vector<StripeRange> ranges;    // item i's objects and shards
+    std::shared_ptr<gpu::FusedPatchPlan> plan;  // built on the first step
+    bool plan_failed = false;  // capture unsupported: stay on launches
+    void end() {
+      token = 0;
+      plan.reset();
+      plan_failed = false;
+    }
+  };
   Result<std::vector<int32_t>> batch_patch_device(
-      const std::vector<DevRangePatch>& items);
+      const std::vector<DevRangePatch>& items,
+      BatchPatchSession* sess = nullptr);
   Result<void> patch_device(const ObjectKey& key, uint64_t offset,
                             const void* dev_ptr, uint64_t length);
   // items patched by the fused_patch launch / by the rewrite route
   uint64_t patched_fused_items() const { return patched_fused_items_; }
   uint64_t patched_rewrite_items() const { return patched_rewrite_items_; }
+  // patch steps served by a session (start by token, one launch, commit by
+  // token); their items count in patched_fused_items too
+  uint64_t session_patch_steps() const { return session_patch_steps_; }
 
   // ---- pipelined batches: begin returns a token immediately; the batch
   // runs on a background thread (metadata RPCs of batch N+1 overlap the
@@ -383,6 +422,7 @@ class GpuClient {
   std::atomic<uint64_t> striped_fused_get_items_{0};
   std::atomic<uint64_t> patched_fused_items_{0};
   std::atomic<uint64_t> patched_rewrite_items_{0};
+  std::atomic<uint64_t> session_patch_steps_{0};
   // the rewrite route of one patch item (info: what the keystone holds)
   Result<void> patch_by_rewrite(const DevRangePatch& item,
                                 const GetWorkersResponse& info);
@@ -395,6 +435,17 @@ class GpuClient {
     std::vector<uint64_t> seg;  // one per segment; empty for the plain form
   };
   Result<StepDigests> session_step(SessionCore& sess, bool put);
+  // The ladder under every session step, patch steps included: build `plan`
+  // lazily (build(plan)), replay it (replay(plan), counted in
+  // session_graph_steps), launch() otherwise; a failed build or replay sets
+  // plan_failed, which keeps the session on launches.
+  template <typename Plan, typename Build, typename Replay, typename Launch>
+  Result<void> step_ladder(std::shared_ptr<Plan>& plan, bool& plan_failed,
+                           const char* what, Build build, Replay replay,
+                           Launch launch);
+  // the patch session's step; nullopt → run the full path
+  std::optional<Result<std::vector<int32_t>>> try_session_patch(
+      const std::vector<DevRangePatch>& items, BatchPatchSession* sess);
   // The warm tail a copy+digest launch of this client asks for, decided here
   // for every path: a put leaves its budget's worth of the batch on-die,
   // and a get loads the same tail plainly (nontemporal loads of resident

@@ -194,6 +194,37 @@ class FusedStripePlan {
   uint32_t nseg_ = 0, nobj_ = 0;
 };
 
+// The same for a patch session (fixed run list every step, other old digests
+// every step): build checks the runs (check_patch_geometry) before any HIP
+// call, uploads {segs | prefix | lens} once and captures H2D of the old
+// digests from the plan's pinned zone → accumulator reset → fused_patch
+// kernel → finalize over the old digests → D2H of the new ones into the same
+// zone, as one chain. run() refuses an old digest of 0 (check_patch_digests)
+// before it launches anything, then is one graph launch and blocks until
+// out_shard_digests[nshard] and out_obj_digests[nobj] are filled; they are
+// what fused_patch gives for the same arguments, bit for bit. size() is the
+// shard count.
+class FusedPatchPlan {
+ public:
+  FusedPatchPlan() = default;
+  ~FusedPatchPlan();
+  FusedPatchPlan(const FusedPatchPlan&) = delete;
+  FusedPatchPlan& operator=(const FusedPatchPlan&) = delete;
+
+  Result<void> build(const PatchSeg* segs, uint32_t nseg,
+                     const uint64_t* shard_lens, uint32_t nshard,
+                     const uint64_t* obj_sizes, uint32_t nobj, int device);
+  bool ready() const { return impl_ != nullptr; }
+  uint32_t size() const { return nshard_; }
+  Result<void> run(const uint64_t* shard_old, const uint64_t* obj_old,
+                   uint64_t* out_shard_digests, uint64_t* out_obj_digests);
+
+ private:
+  struct Impl;
+  Impl* impl_ = nullptr;
+  uint32_t nshard_ = 0, nobj_ = 0;
+};
+
 // Simple utilities used by tests/benchmarks.
 Result<void> fill_pattern(void* dev_ptr, uint64_t nbytes, uint64_t seed,
                           hipStream_t stream);

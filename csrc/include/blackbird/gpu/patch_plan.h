@@ -37,24 +37,15 @@ struct PatchSeg {
   uint32_t obj;         // index into the object arrays
 };
 
-// INVALID_ARGUMENT unless: every index is in range; every run lies inside
-// its shard and its object and covers whole tiles of both — only a run that
-// ends exactly at its object's end, which must be its shard's end too, may
-// end mid-tile (only there does the spec zero-pad); src and dst are 16-byte
-// aligned and [src, src+n) does not overlap [dst, dst+n); no two runs cover
-// the same tile of the same shard (the bytes left behind and the old terms
-// subtracted would depend on wave order); and no old digest is 0, which
-// means "not recorded". Zero-length runs are legal.
-inline Result<void> check_patch_segs(const PatchSeg* segs, uint32_t nseg,
-                                     const uint64_t* shard_lens,
-                                     const uint64_t* shard_old, uint32_t nshard,
-                                     const uint64_t* obj_sizes,
-                                     const uint64_t* obj_old, uint32_t nobj) {
-  using digest::kTileBytes;
-  auto bad = [](uint32_t i, const char* what) {
-    return Error{ErrorCode::INVALID_ARGUMENT,
-                 "patch run " + std::to_string(i) + ": " + what};
-  };
+// The two halves of check_patch_segs. A one-shot launch knows both at once;
+// a replayed step (FusedPatchPlan) knows the runs when it is built and the
+// old digests only when it runs.
+//
+// INVALID_ARGUMENT if an old digest is 0, which means "not recorded".
+inline Result<void> check_patch_digests(const uint64_t* shard_old,
+                                        uint32_t nshard,
+                                        const uint64_t* obj_old,
+                                        uint32_t nobj) {
   for (uint32_t i = 0; i < nshard; ++i)
     if (shard_old[i] == 0)
       return Error{ErrorCode::INVALID_ARGUMENT,
@@ -63,6 +54,26 @@ inline Result<void> check_patch_segs(const PatchSeg* segs, uint32_t nseg,
     if (obj_old[i] == 0)
       return Error{ErrorCode::INVALID_ARGUMENT,
                    "patch object " + std::to_string(i) + ": no recorded digest"};
+  return {};
+}
+
+// INVALID_ARGUMENT unless: every index is in range; every run lies inside
+// its shard and its object and covers whole tiles of both — only a run that
+// ends exactly at its object's end, which must be its shard's end too, may
+// end mid-tile (only there does the spec zero-pad); src and dst are 16-byte
+// aligned and [src, src+n) does not overlap [dst, dst+n); and no two runs
+// cover the same tile of the same shard (the bytes left behind and the old
+// terms subtracted would depend on wave order). Zero-length runs are legal.
+inline Result<void> check_patch_geometry(const PatchSeg* segs, uint32_t nseg,
+                                         const uint64_t* shard_lens,
+                                         uint32_t nshard,
+                                         const uint64_t* obj_sizes,
+                                         uint32_t nobj) {
+  using digest::kTileBytes;
+  auto bad = [](uint32_t i, const char* what) {
+    return Error{ErrorCode::INVALID_ARGUMENT,
+                 "patch run " + std::to_string(i) + ": " + what};
+  };
   // (shard, first tile, tile count, run) of the non-empty runs
   std::vector<std::tuple<uint32_t, uint64_t, uint64_t, uint32_t>> cover;
   for (uint32_t i = 0; i < nseg; ++i) {
@@ -98,6 +109,16 @@ inline Result<void> check_patch_segs(const PatchSeg* segs, uint32_t nseg,
     if (ps == cs && ct < pt + pn) return bad(ci, "covers a tile of another run");
   }
   return {};
+}
+
+// Both: the digests first, then the runs.
+inline Result<void> check_patch_segs(const PatchSeg* segs, uint32_t nseg,
+                                     const uint64_t* shard_lens,
+                                     const uint64_t* shard_old, uint32_t nshard,
+                                     const uint64_t* obj_sizes,
+                                     const uint64_t* obj_old, uint32_t nobj) {
+  BB_RETURN_IF_ERROR(check_patch_digests(shard_old, nshard, obj_old, nobj));
+  return check_patch_geometry(segs, nseg, shard_lens, nshard, obj_sizes, nobj);
 }
 
 // What a byte range touches of one shard of a copy.

@@ -120,6 +120,20 @@ class KeystoneService {
                                    const std::vector<uint64_t>& shard_digests,
                                    bool release = false);
   uint64_t token_commits() const { return ctr_token_commits_.load(); }
+  // BATCH_PATCH_START_TOKEN: batch_patch_start for the objects of a session
+  // (opened while an earlier patch start held them PENDING), by token. All or
+  // nothing: every object must be readable with a recorded checksum and
+  // recorded shard digests, else INVALID_STATE and no object changes state —
+  // a PENDING object too, unlike upsert_start_token: a patch step subtracts
+  // old terms, which torn bytes no longer hold. On success every object is
+  // PENDING with patch_started_ms set and its digests kept, and the answer is
+  // what is recorded now — another writer's re-put in place included — in the
+  // order commit_token_shards, the step's commit, takes the new ones.
+  struct PatchStartDigests {
+    std::vector<uint64_t> obj_digests;
+    std::vector<uint64_t> shard_digests;  // object, copy, shard order
+  };
+  Result<PatchStartDigests> patch_start_token(uint64_t token);
 
   // ------------------------------------------------------ cluster view
   std::vector<WorkerInfo> get_workers_info();

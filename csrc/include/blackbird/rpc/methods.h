@@ -52,6 +52,11 @@ constexpr uint16_t BATCH_COMMIT_TOKEN_SHARDS = 29;
 // BATCH_PUT_COMPLETE; abort puts an unwritten key back to COMMITTED
 constexpr uint16_t BATCH_PATCH_START = 30;
 constexpr uint16_t BATCH_PATCH_ABORT = 31;
+// patch sessions: a session opened (BATCH_SESSION_OPEN) while a patch start
+// held its objects PENDING starts every later step by token — the answer is
+// the recorded checksums and shard digests alone, flat, in the order of
+// BATCH_COMMIT_TOKEN_SHARDS, which is also the step's commit
+constexpr uint16_t BATCH_PATCH_START_TOKEN = 32;
 
 // worker data plane (TCP fallback path; SHM/HIP-IPC paths bypass RPC)
 constexpr uint16_t DATA_WRITE = 200;

@@ -245,7 +245,15 @@ void KeystoneServer::register_handlers() {
                                               c->shard_digests, c->flags & 1));
     return std::string{};
   });
-  leader_only(M::BATCH_REMOVE, [&ks](const std::string& b, const Ctx&) -> Reply {
+  on(M::BATCH_PATCH_START_TOKEN, [&ks](const std::string& b, const Ctx&) -> Reply {
+    auto token = wire::decode_patch_start_token(b);
+    if (!token.ok()) return token.error();
+    auto old = ks.patch_start_token(token.value());
+    if (!old.ok()) return old.error();
+    return wire::encode_patch_start_token_response(
+        {std::move(old->obj_digests), std::move(old->shard_digests)});
+  });
+  leader_only(M::BATCH_REMOVE,[&ks](const std::string& b, const Ctx&) -> Reply {
     auto r = decode<KeysMsg>(b);
     if (!r.ok()) return r.error();
     return serde::to_bytes(StatusListMsg{ks.batch_remove(r->keys)});

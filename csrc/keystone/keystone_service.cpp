@@ -793,6 +793,45 @@ Result<void> KeystoneService::upsert_start_token(uint64_t token) {
   return {};
 }
 
+Result<KeystoneService::PatchStartDigests> KeystoneService::patch_start_token(
+    uint64_t token) {
+  if (!is_leader()) return not_leader();
+  auto s = find_session(token);
+  if (!s) return Error{ErrorCode::SESSION_STALE, "unknown put session"};
+  const uint64_t now = now_ms();
+  // exclusive, as batch_patch_start: two starts that share a key must not
+  // both find it COMMITTED
+  std::unique_lock lk(objects_mu_);
+  BB_RETURN_IF_ERROR(session_current_locked(*s));
+  PatchStartDigests out;
+  out.obj_digests.reserve(s->metas.size());
+  out.shard_digests.reserve(s->total_shards);
+  // validate ALL before flipping ANY
+  for (const ObjectMeta* m : s->metas) {
+    if (readable(m, now) != ErrorCode::OK)
+      return Error{ErrorCode::INVALID_STATE, "not readable: " + m->key};
+    if (m->checksum == 0)
+      return Error{ErrorCode::INVALID_STATE, "no recorded checksum: " + m->key};
+    out.obj_digests.push_back(m->checksum);
+    for (const auto& c : m->copies)
+      for (const auto& sh : c.shards) {
+        if (sh.digest == 0)
+          return Error{ErrorCode::INVALID_STATE,
+                       "no recorded shard digest: " + m->key};
+        out.shard_digests.push_back(sh.digest);
+      }
+  }
+  // a single-shard session never had its shape compared (see
+  // session_current_locked); the count is what the commit will be held to
+  if (out.shard_digests.size() != s->total_shards)
+    return Error{ErrorCode::SESSION_STALE, "object shape changed"};
+  for (ObjectMeta* m : s->metas) {
+    m->patch_started_ms = now ? now : 1;
+    m->state = ObjectState::PENDING;
+  }
+  return out;
+}
+
 Result<void> KeystoneService::commit_token(
     uint64_t token, const std::vector<uint64_t>& digests, bool release) {
   if (!is_leader()) return not_leader();
