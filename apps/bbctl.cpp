@@ -17,6 +17,10 @@ static void usage() {
       "  get <key> [file]        fetch an object (stdout by default)\n"
       "      --range OFF:LEN     only these bytes (unverified)\n"
       "  patch <key> <off> <file|->   overwrite bytes of an object in place\n"
+      "      --edge-tiles        any range in place: tiles patched in part are\n"
+      "                          composed of old and new bytes; the object is\n"
+      "                          not re-verified (default: such a range rewrites\n"
+      "                          and verifies the whole object)\n"
       "  rm <key>                remove an object\n"
       "  exists <key>\n"
       "  stat                    cluster stats\n"
@@ -50,6 +54,8 @@ int main(int argc, char** argv) {
       ranged = true;
       range_off = strtoull(r.substr(0, colon).c_str(), nullptr, 0);
       range_len = strtoull(r.substr(colon + 1).c_str(), nullptr, 0);
+    } else if (a == "--edge-tiles") {
+      opts.patch_edge_tiles = true;
     } else if (a == "--class") {
       auto c = storage_class_from_string(next());
       if (c) pcfg.preferred_class = *c;

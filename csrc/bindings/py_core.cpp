@@ -687,10 +687,25 @@ PYBIND11_MODULE(_core, m) {
                     obj});
     return ss;
   };
-  gm.def("fused_patch", [to_patch_segs](const PatchTuples& segs,
-                                        const U64s& shard_lens, const U64s& shard_old,
-                                        const U64s& obj_sizes, const U64s& obj_old) {
+  // edges are (src, tile, lo, hi, valid, shard_tile, obj_tile, shard, obj)
+  // tuples, a trailing optional argument wherever runs are taken
+  using EdgeTuples =
+      std::vector<std::tuple<uint64_t, uint64_t, uint32_t, uint32_t, uint32_t,
+                             uint64_t, uint64_t, uint32_t, uint32_t>>;
+  auto to_patch_edges = [](const EdgeTuples& edges) {
+    std::vector<gpu::PatchEdge> es;
+    for (auto& [src, tile, lo, hi, valid, shard_tile, obj_tile, shard, obj] : edges)
+      es.push_back({reinterpret_cast<const void*>(src),
+                    reinterpret_cast<void*>(tile), lo, hi, valid, shard_tile,
+                    obj_tile, shard, obj});
+    return es;
+  };
+  gm.def("fused_patch", [to_patch_segs, to_patch_edges](
+                            const PatchTuples& segs, const U64s& shard_lens,
+                            const U64s& shard_old, const U64s& obj_sizes,
+                            const U64s& obj_old, const EdgeTuples& edges) {
     auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+    auto es = to_patch_edges(edges);
     // poisoned, as in fused_put
     U64s shard_out(shard_lens.size(), ~0ull), obj_out(obj_sizes.size(), ~0ull);
     py::gil_scoped_release rel;
@@ -698,25 +713,53 @@ PYBIND11_MODULE(_core, m) {
         ss.data(), static_cast<uint32_t>(ss.size()), shard_lens.data(),
         shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
         obj_sizes.data(), obj_old.data(), static_cast<uint32_t>(obj_sizes.size()),
-        shard_out.data(), obj_out.data(), nullptr));
+        shard_out.data(), obj_out.data(), nullptr, es.data(),
+        static_cast<uint32_t>(es.size())));
     return std::make_pair(shard_out, obj_out);
   }, py::arg("segs"), py::arg("shard_lens"), py::arg("shard_old"),
-     py::arg("obj_sizes"), py::arg("obj_old"));
+     py::arg("obj_sizes"), py::arg("obj_old"), py::arg("edges") = EdgeTuples{});
   gm.def("patch_walk_depth", &gpu::patch_walk_depth);
   // the argument check of fused_patch alone (no GPU): raises INVALID_ARGUMENT
-  gm.def("check_patch_segs", [to_patch_segs](const PatchTuples& segs,
-                                             const U64s& shard_lens,
-                                             const U64s& shard_old,
-                                             const U64s& obj_sizes,
-                                             const U64s& obj_old) {
+  gm.def("check_patch_segs", [to_patch_segs, to_patch_edges](
+                                 const PatchTuples& segs, const U64s& shard_lens,
+                                 const U64s& shard_old, const U64s& obj_sizes,
+                                 const U64s& obj_old, const EdgeTuples& edges) {
     auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+    auto es = to_patch_edges(edges);
     unwrap_void(gpu::check_patch_segs(
         ss.data(), static_cast<uint32_t>(ss.size()), shard_lens.data(),
         shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
         obj_sizes.data(), obj_old.data(),
         static_cast<uint32_t>(obj_sizes.size())));
+    unwrap_void(gpu::check_patch_edges(
+        es.data(), static_cast<uint32_t>(es.size()), ss.data(),
+        static_cast<uint32_t>(ss.size()), shard_lens.data(),
+        static_cast<uint32_t>(shard_lens.size()), obj_sizes.data(),
+        static_cast<uint32_t>(obj_sizes.size())));
   }, py::arg("segs"), py::arg("shard_lens"), py::arg("shard_old"),
-     py::arg("obj_sizes"), py::arg("obj_old"));
+     py::arg("obj_sizes"), py::arg("obj_old"), py::arg("edges") = EdgeTuples{});
+  // the edge rules alone, against runs that passed the check above
+  gm.def("check_patch_edges", [to_patch_edges](const EdgeTuples& edges,
+                                               const PatchTuples& segs,
+                                               const U64s& shard_lens,
+                                               const U64s& obj_sizes) {
+    std::vector<gpu::PatchSeg> ss;
+    for (auto& [src, dst, n, shard_tile, obj_tile, shard, obj] : segs)
+      ss.push_back({reinterpret_cast<const void*>(src),
+                    reinterpret_cast<void*>(dst), n, shard_tile, obj_tile, shard,
+                    obj});
+    auto es = to_patch_edges(edges);
+    unwrap_void(gpu::check_patch_geometry(
+        ss.data(), static_cast<uint32_t>(ss.size()), shard_lens.data(),
+        static_cast<uint32_t>(shard_lens.size()), obj_sizes.data(),
+        static_cast<uint32_t>(obj_sizes.size())));
+    unwrap_void(gpu::check_patch_edges(
+        es.data(), static_cast<uint32_t>(es.size()), ss.data(),
+        static_cast<uint32_t>(ss.size()), shard_lens.data(),
+        static_cast<uint32_t>(shard_lens.size()), obj_sizes.data(),
+        static_cast<uint32_t>(obj_sizes.size())));
+  }, py::arg("edges"), py::arg("segs"), py::arg("shard_lens"),
+     py::arg("obj_sizes"));
   // a byte range of one copy → [(shard, shard_off, obj_off, nbytes)];
   // plan_patch: None = not patchable in place; range_pieces: None = the range
   // leaves the object or the lengths do not add up
@@ -733,6 +776,25 @@ PYBIND11_MODULE(_core, m) {
   gm.def("plan_patch", [to_piece_tuples](uint64_t obj_size, const U64s& shard_lens,
                                          uint64_t offset, uint64_t length) {
     return to_piece_tuples(gpu::plan_patch(obj_size, shard_lens, offset, length));
+  }, py::arg("obj_size"), py::arg("shard_lens"), py::arg("offset"),
+     py::arg("length"));
+  // the same at byte granularity: (runs, edges), runs as plan_patch's pieces,
+  // edges as (shard, shard_tile, obj_tile, lo, hi, valid, src_off); None =
+  // plan_stripe refuses the copy or the range leaves the object
+  gm.def("plan_patch_bytes", [to_piece_tuples](uint64_t obj_size,
+                                               const U64s& shard_lens,
+                                               uint64_t offset, uint64_t length)
+      -> std::optional<std::pair<
+          PieceTuples, std::vector<std::tuple<uint32_t, uint64_t, uint64_t, uint32_t,
+                                              uint32_t, uint32_t, uint64_t>>>> {
+    auto plan = gpu::plan_patch_bytes(obj_size, shard_lens, offset, length);
+    if (!plan) return std::nullopt;
+    std::vector<std::tuple<uint32_t, uint64_t, uint64_t, uint32_t, uint32_t,
+                           uint32_t, uint64_t>> edges;
+    for (const auto& e : plan->edges)
+      edges.emplace_back(e.shard, e.shard_tile, e.obj_tile, e.lo, e.hi, e.valid,
+                         e.src_off);
+    return std::make_pair(*to_piece_tuples(plan->runs), edges);
   }, py::arg("obj_size"), py::arg("shard_lens"), py::arg("offset"),
      py::arg("length"));
   gm.def("range_pieces", [to_piece_tuples](uint64_t obj_size, const U64s& shard_lens,
@@ -800,10 +862,12 @@ PYBIND11_MODULE(_core, m) {
   // are step k-1's outputs; the first step takes the given ones.
   // before_step(k), when given, runs before replay k.
   gm.def("fused_patch_plan",
-         [to_patch_segs](const PatchTuples& segs, const U64s& shard_lens,
-                         const U64s& obj_sizes, U64s shard_old, U64s obj_old,
-                         int steps, int device, py::object before_step) {
+         [to_patch_segs, to_patch_edges](
+             const PatchTuples& segs, const U64s& shard_lens,
+             const U64s& obj_sizes, U64s shard_old, U64s obj_old, int steps,
+             int device, py::object before_step, const EdgeTuples& edges) {
            auto ss = to_patch_segs(segs, shard_lens, shard_old, obj_sizes, obj_old);
+           auto es = to_patch_edges(edges);
            std::vector<std::pair<U64s, U64s>> out;
            gpu::FusedPatchPlan plan;
            {
@@ -813,7 +877,8 @@ PYBIND11_MODULE(_core, m) {
                                     static_cast<uint32_t>(shard_lens.size()),
                                     obj_sizes.data(),
                                     static_cast<uint32_t>(obj_sizes.size()),
-                                    device));
+                                    device, es.data(),
+                                    static_cast<uint32_t>(es.size())));
            }
            for (int k = 0; k < steps; ++k) {
              if (!before_step.is_none()) before_step(k);
@@ -831,7 +896,8 @@ PYBIND11_MODULE(_core, m) {
            return out;
          }, py::arg("segs"), py::arg("shard_lens"), py::arg("obj_sizes"),
          py::arg("shard_old"), py::arg("obj_old"), py::arg("steps"),
-         py::arg("device") = 0, py::arg("before_step") = py::none());
+         py::arg("device") = 0, py::arg("before_step") = py::none(),
+         py::arg("edges") = EdgeTuples{});
   gm.def("batched_copy",
          [](const std::vector<std::tuple<uint64_t, uint64_t, uint64_t>>& descs) {
            std::vector<gpu::CopyDesc> ds;

@@ -370,6 +370,7 @@ void bind_store(py::module_& m) {
       .def_readwrite("coord_endpoint", &ClientOptions::coord_endpoint)
       .def_readwrite("io_threads", &ClientOptions::io_threads)
       .def_readwrite("verify_checksum_on_get", &ClientOptions::verify_checksum_on_get)
+      .def_readwrite("patch_edge_tiles", &ClientOptions::patch_edge_tiles)
       .def_readwrite("rpc_timeout_ms", &ClientOptions::rpc_timeout_ms)
       .def_readwrite("force_tcp", &ClientOptions::force_tcp);
 
@@ -592,6 +593,9 @@ void bind_store(py::module_& m) {
       .def("set_warm_tail_bytes", &GpuClient::set_warm_tail_bytes,
            py::arg("bytes"))
       .def_property_readonly("warm_tail_bytes", &GpuClient::warm_tail_bytes)
+      .def("set_patch_edge_tiles", &GpuClient::set_patch_edge_tiles,
+           py::arg("on"))
+      .def_property_readonly("patch_edge_tiles", &GpuClient::patch_edge_tiles)
       .def("put_device", [](GpuClient& g, const std::string& key, uint64_t ptr,
                             uint64_t size, const PlacementConfig& cfg) {
         unwrap_void(g.put_device(key, reinterpret_cast<const void*>(ptr), size, cfg));

@@ -534,19 +534,58 @@ Result<void> Client::patch(const ObjectKey& key, uint64_t offset,
     return Error{ErrorCode::INVALID_ARGUMENT, "range past the end of " + key};
   }
 
+  using digest::kTileBytes;
+  // a piece rounded out to whole tiles of its shard, clipped at the shard's
+  // end: what has to be read to move the digests by it. A piece of whole
+  // tiles, or one from a tile boundary to the object's end, is its own.
+  auto rounded = [](const gpu::RangePiece& p, uint64_t shard_len) {
+    const uint64_t head = p.shard_off % kTileBytes;
+    const uint64_t end = p.shard_off + p.nbytes;
+    const uint64_t stop = std::min(
+        shard_len, (end + kTileBytes - 1) / kTileBytes * kTileBytes);
+    return gpu::RangePiece{p.shard, p.shard_off - head, p.obj_off - head,
+                           stop - (p.shard_off - head)};
+  };
   // every copy's pieces, or the rewrite route
   std::vector<std::vector<gpu::RangePiece>> plans;
   bool in_place = !info.copies.empty();
   for (const auto& copy : info.copies) {
-    auto pieces = gpu::plan_patch(info.size, shard_lens_of(copy), offset, size);
+    std::optional<std::vector<gpu::RangePiece>> pieces;
+    if (opts_.patch_edge_tiles) {
+      // runs and edge tiles of one shard lie back to back: the bytes written
+      // there are one piece again, in shard order
+      if (auto plan = gpu::plan_patch_bytes(info.size, shard_lens_of(copy),
+                                            offset, size)) {
+        std::vector<gpu::RangePiece> all = std::move(plan->runs);
+        for (const auto& e : plan->edges)
+          all.push_back({e.shard, e.shard_tile * kTileBytes + e.lo,
+                         e.obj_tile * kTileBytes + e.lo, uint64_t{e.hi} - e.lo});
+        std::sort(all.begin(), all.end(), [](const auto& a, const auto& b) {
+          return a.obj_off < b.obj_off;
+        });
+        pieces.emplace();
+        for (const auto& p : all) {
+          if (!pieces->empty() && pieces->back().shard == p.shard)
+            pieces->back().nbytes += p.nbytes;
+          else
+            pieces->push_back(p);
+        }
+      }
+    } else {
+      pieces = gpu::plan_patch(info.size, shard_lens_of(copy), offset, size);
+    }
     if (!pieces) {
       in_place = false;
       break;
     }
     for (const auto& s : copy.shards)
       if (s.digest == 0) in_place = false;
-    for (const auto& p : *pieces)
-      if (!sub_shard_ok(copy.shards[p.shard], p)) in_place = false;
+    for (const auto& p : *pieces) {
+      const auto& shard = copy.shards[p.shard];
+      if (!sub_shard_ok(shard, p) ||
+          !sub_shard_ok(shard, rounded(p, shard.length)))
+        in_place = false;
+    }
     plans.push_back(std::move(*pieces));
   }
   if (!in_place) {
@@ -556,9 +595,9 @@ Result<void> Client::patch(const ObjectKey& key, uint64_t offset,
 
   // old bytes first — nothing is written until every copy's new digests are
   // known and agree
-  using digest::kTileBytes;
   PutCompleteRequest done_req{key, 0, {}};
   std::string old(size, '\0');
+  std::string edge_old, edge_new;  // a piece with edge tiles, rounded out
   for (size_t c = 0; c < info.copies.size(); ++c) {
     const auto& copy = info.copies[c];
     uint64_t h = gpu::checksum_cpu_unfinalize(info.checksum, info.size);
@@ -567,17 +606,32 @@ Result<void> Client::patch(const ObjectKey& key, uint64_t offset,
       sums.push_back(gpu::checksum_cpu_unfinalize(s.digest, s.length));
     for (const auto& p : plans[c]) {
       const uint64_t at = p.obj_off - offset;
-      auto r = read_shard(sub_shard(copy.shards[p.shard], p.shard_off, p.nbytes),
-                          old.data() + at);
+      // the tiles the piece touches: their old bytes, and what they become
+      const gpu::RangePiece t = rounded(p, copy.shards[p.shard].length);
+      const bool edges = t.nbytes != p.nbytes;
+      char* old_t = old.data() + at;
+      const void* new_t = new_bytes + at;
+      if (edges) {
+        edge_old.resize(t.nbytes);
+        old_t = edge_old.data();
+      }
+      auto r = read_shard(sub_shard(copy.shards[p.shard], t.shard_off, t.nbytes),
+                          old_t);
       if (!r.ok()) {
         patch_abort({key});
         return r.error();
       }
-      const uint64_t ot = p.obj_off / kTileBytes, st = p.shard_off / kTileBytes;
-      h += gpu::checksum_cpu_tiles(new_bytes + at, p.nbytes, ot) -
-           gpu::checksum_cpu_tiles(old.data() + at, p.nbytes, ot);
-      sums[p.shard] += gpu::checksum_cpu_tiles(new_bytes + at, p.nbytes, st) -
-                       gpu::checksum_cpu_tiles(old.data() + at, p.nbytes, st);
+      if (edges) {  // composed of old and new bytes
+        edge_new = edge_old;
+        std::memcpy(edge_new.data() + (p.shard_off - t.shard_off),
+                    new_bytes + at, p.nbytes);
+        new_t = edge_new.data();
+      }
+      const uint64_t ot = t.obj_off / kTileBytes, st = t.shard_off / kTileBytes;
+      h += gpu::checksum_cpu_tiles(new_t, t.nbytes, ot) -
+           gpu::checksum_cpu_tiles(old_t, t.nbytes, ot);
+      sums[p.shard] += gpu::checksum_cpu_tiles(new_t, t.nbytes, st) -
+                       gpu::checksum_cpu_tiles(old_t, t.nbytes, st);
     }
     const uint64_t checksum = gpu::checksum_cpu_finalize(h, info.size);
     if (c > 0 && checksum != done_req.checksum) {

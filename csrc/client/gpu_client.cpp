@@ -814,6 +814,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
   // its own, so diverged replicas show as different digests. An item's range
   // counts shards (the digest lists), not the patched pieces.
   std::vector<gpu::PatchSeg> segs;
+  std::vector<gpu::PatchEdge> edges;  // patch_edge_tiles_: tiles patched in part
   std::vector<uint64_t> shard_lens, shard_old, obj_sizes, obj_old;
   std::vector<uint32_t> copy_shards;  // per kernel object; a session keeps it
   std::vector<StripeRange> fused;
@@ -846,13 +847,24 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
       aborts.push_back(it.key);
       continue;
     }
-    const size_t seg_mark = segs.size(), shard_mark = shard_lens.size(),
-                 obj_mark = obj_sizes.size();
+    const size_t seg_mark = segs.size(), edge_mark = edges.size(),
+                 shard_mark = shard_lens.size(), obj_mark = obj_sizes.size();
     bool in_place = !info.copies.empty();
     for (size_t c = 0; in_place && c < info.copies.size(); ++c) {
       const auto& copy = info.copies[c];
-      auto pieces =
-          gpu::plan_patch(info.size, shard_lens_of(copy), it.offset, it.length);
+      // whole-tile runs, and with patch_edge_tiles_ the edge tiles around them
+      std::optional<std::vector<gpu::RangePiece>> pieces;
+      std::vector<gpu::EdgePiece> edge_pieces;
+      if (patch_edge_tiles_) {
+        if (auto plan = gpu::plan_patch_bytes(info.size, shard_lens_of(copy),
+                                              it.offset, it.length)) {
+          pieces = std::move(plan->runs);
+          edge_pieces = std::move(plan->edges);
+        }
+      } else {
+        pieces = gpu::plan_patch(info.size, shard_lens_of(copy), it.offset,
+                                 it.length);
+      }
       if (!pieces) {
         in_place = false;
         break;
@@ -879,9 +891,23 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
                         p.shard_off / digest::kTileBytes,
                         p.obj_off / digest::kTileBytes, shard0 + p.shard, obj});
       }
+      // edges go byte by byte: any device-visible address will do
+      for (size_t k = 0; in_place && k < edge_pieces.size(); ++k) {
+        const auto& e = edge_pieces[k];
+        uint8_t* pool = resolve_device_ptr(copy.shards[e.shard]);
+        if (!pool) {
+          in_place = false;
+          break;
+        }
+        edges.push_back({static_cast<const uint8_t*>(it.ptr) + e.src_off,
+                         pool + e.shard_tile * digest::kTileBytes, e.lo, e.hi,
+                         e.valid, e.shard_tile, e.obj_tile, shard0 + e.shard,
+                         obj});
+      }
     }
     if (!in_place) {
       segs.resize(seg_mark);
+      edges.resize(edge_mark);
       shard_lens.resize(shard_mark);
       shard_old.resize(shard_mark);
       obj_sizes.resize(obj_mark);
@@ -904,7 +930,8 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
         segs.data(), static_cast<uint32_t>(segs.size()), shard_lens.data(),
         shard_old.data(), static_cast<uint32_t>(shard_lens.size()),
         obj_sizes.data(), obj_old.data(), static_cast<uint32_t>(obj_sizes.size()),
-        shard_new.data(), obj_new.data(), streams_[2]);
+        shard_new.data(), obj_new.data(), streams_[2], edges.data(),
+        static_cast<uint32_t>(edges.size()));
     std::vector<ObjectKey> cancels;
     std::vector<PutCompleteRequest> reqs;
     std::vector<uint32_t> order;
@@ -941,6 +968,7 @@ Result<std::vector<int32_t>> GpuClient::batch_patch_device(
           sess->token = t.value();
           sess->bound = items;
           sess->segs = std::move(segs);
+          sess->edges = std::move(edges);
           sess->shard_lens = std::move(shard_lens);
           sess->obj_sizes = std::move(obj_sizes);
           sess->copy_shards = std::move(copy_shards);
@@ -989,6 +1017,8 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_patch(
     same = a.key == b.key && a.offset == b.offset && a.ptr == b.ptr &&
            a.length == b.length;
   }
+  // a session that patches edge tiles lives only while the option is on
+  if (!sess->edges.empty() && !patch_edge_tiles_) same = false;
   if (!same) {
     sess->end();
     return std::nullopt;
@@ -1028,13 +1058,16 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_patch(
 
   const gpu::PatchSeg* segs = sess->segs.data();
   const uint32_t nseg = static_cast<uint32_t>(sess->segs.size());
+  const gpu::PatchEdge* edges = sess->edges.data();
+  const uint32_t nedge = static_cast<uint32_t>(sess->edges.size());
   const uint64_t* lens = sess->shard_lens.data();
   const uint64_t* sizes = sess->obj_sizes.data();
   std::vector<uint64_t> shard_new(nshard), obj_new(nobj);
   auto launched = step_ladder(
       sess->plan, sess->plan_failed, "patch ",
       [&](auto& p) {
-        return p.build(segs, nseg, lens, nshard, sizes, nobj, device_);
+        return p.build(segs, nseg, lens, nshard, sizes, nobj, device_, edges,
+                       nedge);
       },
       [&](auto& p) {
         return p.run(shard_old.data(), obj_old.data(), shard_new.data(),
@@ -1043,7 +1076,7 @@ std::optional<Result<std::vector<int32_t>>> GpuClient::try_session_patch(
       [&] {
         return gpu::fused_patch(segs, nseg, lens, shard_old.data(), nshard,
                                 sizes, obj_old.data(), nobj, shard_new.data(),
-                                obj_new.data(), streams_[2]);
+                                obj_new.data(), streams_[2], edges, nedge);
       });
   std::vector<int32_t> statuses(items.size(), 0);
   auto torn = [&](ErrorCode code) {  // every key cancelled, the session over

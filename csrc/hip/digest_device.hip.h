@@ -213,6 +213,40 @@ __device__ inline void store_a_frag_guarded(uint8_t* base, uint64_t tile_off,
     if (off + j < nbytes) g[off + j] = static_cast<uint8_t>(ab[j]);
 }
 
+// The windowed pair of an edge tile (patch_edge_tile): tile positions
+// [lo, hi) take the bytes at src, src[0] being position lo; every other
+// position keeps the lane's byte of `old`. Nothing of src is read outside
+// [src, src + hi - lo).
+__device__ inline i32x4 compose_a_frag_windowed(const i32x4& old,
+                                                const uint8_t* src, uint32_t lo,
+                                                uint32_t hi, uint32_t lane_off) {
+  union {
+    int8_t b[16];
+    i32x4 v;
+  } u;
+  u.v = old;
+  const global_ptr<const uint8_t> g = as_global(src);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const uint32_t p = lane_off + j;
+    if (p >= lo && p < hi) u.b[j] = static_cast<int8_t>(g[p - lo]);
+  }
+  return u.v;
+}
+
+// ... and only the positions [lo, hi) are written.
+__device__ inline void store_a_frag_windowed(uint8_t* tile, uint32_t lo,
+                                             uint32_t hi, uint32_t lane_off,
+                                             const i32x4& a) {
+  const global_ptr<uint8_t> g = as_global(tile);
+  const int8_t* ab = reinterpret_cast<const int8_t*>(&a);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const uint32_t p = lane_off + j;
+    if (p >= lo && p < hi) g[p] = static_cast<uint8_t>(ab[j]);
+  }
+}
+
 __device__ inline uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
@@ -627,6 +661,52 @@ __device__ __forceinline__ void patch_walk(
   };
   walk_descs(segs, tile_prefix, nseg, begin, end, enter, leave, full_run,
              tail_tile);
+}
+
+// One edge tile of a byte-granular patch (patch.hip), one wave: the tile is
+// overwritten in part, [lo, hi) of it, and moves its shard's and its object's
+// sums by term(composed tile) − term(old tile), into the accumulators the
+// patch walk adds to. The old tile is loaded with the byte path (zero past
+// valid, nothing read there), the composed fragment takes src's bytes inside
+// the window, and only the window is stored — after every load has returned,
+// waited for explicitly as in the walk's tail tile, so nothing leans on the
+// memory system's order between a load and a younger store to one address.
+// check_patch_edges keeps every other wave of the launch, and the run kernel
+// before it on the stream, off this tile.
+__device__ __forceinline__ void patch_edge_tile(
+    const PatchEdge& d, int lane, unsigned long long* __restrict__ shard_acc,
+    unsigned long long* __restrict__ obj_acc) {
+  const uint8_t* src = wave_uniform(static_cast<const uint8_t*>(d.src));
+  uint8_t* tile = wave_uniform(static_cast<uint8_t*>(d.tile));
+  const uint32_t lo = wave_uniform(d.lo);
+  const uint32_t hi = wave_uniform(d.hi);
+  const uint32_t valid = wave_uniform(d.valid);
+  const uint64_t shard_slot = wave_uniform(d.shard_tile) * 64;
+  const uint64_t obj_slot = wave_uniform(d.obj_tile) * 64;
+  const uint32_t shard = wave_uniform(d.shard);
+  const uint32_t obj = wave_uniform(d.obj);
+
+  const i32x4 b_frag = load_b_frag(lane);
+  const WReg wr = load_w_reg(lane);
+  const uint32_t lane_off = lane_tile_offset(lane);
+
+  const i32x4 a_old = load_a_frag_guarded(tile, 0, valid, lane_off);
+  const i32x4 a_new = compose_a_frag_windowed(a_old, src, lo, hi, lane_off);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  store_a_frag_windowed(tile, lo, hi, lane_off, a_new);
+
+  const uint64_t f_old = fold_group(project_tile(a_old, b_frag), wr);
+  const uint64_t f_new = fold_group(project_tile(a_new, b_frag), wr);
+  uint64_t hs = mix_slot(f_new, shard_slot + lane) -
+                mix_slot(f_old, shard_slot + lane);
+  uint64_t ho = 0;
+  if (shard_slot != obj_slot)
+    ho = mix_slot(f_new, obj_slot + lane) - mix_slot(f_old, obj_slot + lane);
+  hs = wave_sum_u64(hs);
+  if (shard_slot != obj_slot) ho = wave_sum_u64(ho);
+  else ho = hs;
+  if (lane == 0 && hs != 0) atomicAdd(&shard_acc[shard], hs);
+  if (lane == 0 && ho != 0) atomicAdd(&obj_acc[obj], ho);
 }
 
 }  // namespace blackbird::gpu::dev

@@ -42,6 +42,10 @@ struct ClientOptions {
   std::string cluster_id = "default";
   int io_threads = 4;
   bool verify_checksum_on_get = false;  // digests verified on demand
+  // patch() at byte granularity: a range that is not whole 1 KiB tiles is
+  // patched in place too, its edge tiles composed of old and new bytes.
+  // Off: such a range takes the rewrite route, which verifies the object.
+  bool patch_edge_tiles = false;
   int rpc_timeout_ms = 30000;
   // diagnostics / transport comparison: skip the one-sided SHM/IPC fast
   // paths and go through the worker data plane (TCP) only
@@ -82,6 +86,13 @@ class Client {
   // that ends at the object's end), an object without recorded digests, or
   // a copy that cannot be patched shard by shard takes the rewrite route:
   // get the object, overlay the range, put it back with replace=true.
+  // With ClientOptions::patch_edge_tiles the copy is planned with
+  // gpu::plan_patch_bytes and any range is patched in place: per shard the
+  // range is read ROUNDED OUT to whole tiles (clipped at the object's end),
+  // the new tiles are composed of old and new bytes, the sums move by
+  // checksum_cpu_tiles(new) − checksum_cpu_tiles(old) over the rounded range,
+  // and only the new bytes are written. Unlike the rewrite route this does
+  // not verify the object first: a corrupt byte stays, and stays detectable.
   // Replicas whose patched digests disagree: CHECKSUM_MISMATCH, nothing
   // written. A write that fails midway leaves torn bytes: the key is
   // cancelled (removed), as after a failed in-place upsert.

@@ -208,6 +208,19 @@ class GpuClient {
   // every put and get session bound to them; other clients' cached verified
   // gets mismatch and fall back to the RPC path.
   //
+  // Byte granularity (set_patch_edge_tiles(true), default off): each copy is
+  // planned with gpu::plan_patch_bytes, and a range that is not whole tiles
+  // rides the SAME launch as whole-tile runs between at most two edge tiles,
+  // each composed on the GPU of its old bytes and the new ones
+  // (gpu::PatchEdge). Only the patched tiles are read, so — unlike the rewrite
+  // route, which verifies the whole object — a corrupt byte outside the range
+  // is not noticed here; it stays detectable, the digests move by differences.
+  // Still on the rewrite route: an item whose interior run's source and pool
+  // address are not both 16B-aligned (the caller's pointer and the offset
+  // must share their phase mod 16), a pool that does not resolve, a shard
+  // without a digest. Edge tiles ask no alignment. Sessions keep the edge
+  // list with the run list, so unaligned items establish and replay one.
+  //
   // Patch sessions: a caller that patches the SAME item list (keys, offsets,
   // buffers, lengths, order) every step passes a session object. The first
   // call runs the path above and, if every item rode the fused launch and
@@ -231,6 +244,7 @@ class GpuClient {
     std::vector<DevRangePatch> bound;  // the item list the lists below serve
     // the fused_patch argument lists but for the old digests
     std::vector<gpu::PatchSeg> segs;
+    std::vector<gpu::PatchEdge> edges;  // set_patch_edge_tiles: may be all
     std::vector<uint64_t> shard_lens, obj_sizes;
     std::vector<uint32_t> copy_shards;  // shards of each kernel object
     std::vector<StripeRange> ranges;    // item i's objects and shards
@@ -284,6 +298,11 @@ class GpuClient {
   static constexpr uint64_t kDefaultWarmTailBytes = 128ull << 20;
   void set_warm_tail_bytes(uint64_t bytes) { warm_tail_bytes_ = bytes; }
   uint64_t warm_tail_bytes() const { return warm_tail_bytes_; }
+
+  // In-place patches at byte granularity (batch_patch_device above). Off:
+  // every range that is not whole tiles takes the rewrite route.
+  void set_patch_edge_tiles(bool on) { patch_edge_tiles_ = on; }
+  bool patch_edge_tiles() const { return patch_edge_tiles_; }
 
   // ---- collective batch shuffle (RCCL over xGMI; see shuffle.h) ----
   // Every rank calls this together: want[p] lists the objects this rank
@@ -456,6 +475,7 @@ class GpuClient {
   Result<uint64_t> submit_async(Fn fn);
   bool fused_copy_ = true;
   uint64_t warm_tail_bytes_ = kDefaultWarmTailBytes;
+  bool patch_edge_tiles_ = false;
   bool initialized_ = false;
 };
 

@@ -132,12 +132,21 @@ Result<void> fused_stripe(const StripeSeg* segs, uint32_t nseg,
 // go through check_patch_segs (patch_plan.h) before any HIP call. All arrays
 // are HOST arrays (call blocks on `stream`; nullptr = a stream of the shared
 // transfer pool). After an error past the check, the runs' bytes are torn.
+//
+// edges: tiles overwritten in part (PatchEdge, patch_plan.h), the head and the
+// tail of a range that is not whole tiles. A second kernel on the same stream,
+// one wave per edge, composes each tile of its old bytes and the new ones in
+// [lo, hi), stores only those, and adds term(composed) − term(old) to the same
+// sums; they go through check_patch_edges with the runs. No alignment is
+// asked of an edge. A launch of edges alone (nseg == 0) is legal; with no
+// edge the HIP calls are those of a launch of runs.
 Result<void> fused_patch(const PatchSeg* segs, uint32_t nseg,
                          const uint64_t* shard_lens, const uint64_t* shard_old,
                          uint32_t nshard, const uint64_t* obj_sizes,
                          const uint64_t* obj_old, uint32_t nobj,
                          uint64_t* out_shard_digests, uint64_t* out_obj_digests,
-                         hipStream_t stream);
+                         hipStream_t stream, const PatchEdge* edges = nullptr,
+                         uint32_t nedge = 0);
 // Depth of fused_patch's load pipeline, per stream (old and new): a run of
 // full tiles enters its steady loop from 3 * depth tiles on. For tests to
 // size themselves, as digest_walk_depth.
@@ -203,7 +212,9 @@ class FusedStripePlan {
 // before it launches anything, then is one graph launch and blocks until
 // out_shard_digests[nshard] and out_obj_digests[nobj] are filled; they are
 // what fused_patch gives for the same arguments, bit for bit. size() is the
-// shard count.
+// shard count. Edges ride the plan as they ride fused_patch: checked with the
+// runs, uploaded with them, their kernel one more node of the chain between
+// the run kernel and finalize; a plan of edges alone is legal.
 class FusedPatchPlan {
  public:
   FusedPatchPlan() = default;
@@ -213,7 +224,8 @@ class FusedPatchPlan {
 
   Result<void> build(const PatchSeg* segs, uint32_t nseg,
                      const uint64_t* shard_lens, uint32_t nshard,
-                     const uint64_t* obj_sizes, uint32_t nobj, int device);
+                     const uint64_t* obj_sizes, uint32_t nobj, int device,
+                     const PatchEdge* edges = nullptr, uint32_t nedge = 0);
   bool ready() const { return impl_ != nullptr; }
   uint32_t size() const { return nshard_; }
   Result<void> run(const uint64_t* shard_old, const uint64_t* obj_old,

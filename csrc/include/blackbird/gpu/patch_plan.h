@@ -170,4 +170,152 @@ inline std::optional<std::vector<RangePiece>> plan_patch(
   return range_pieces(obj_size, shard_lens, offset, length);
 }
 
+// ------------------------------------------------ byte-granular patches
+// A tile's term depends only on its 1024 bytes and its slot, so a tile that is
+// overwritten IN PART moves a digest by term(composed tile) − term(old tile),
+// the composed tile being the old bytes outside [lo, hi) and the new bytes
+// inside. Such a tile is an EDGE of a byte range: at most one at its head and
+// one at its tail, with whole-tile runs (PatchSegs) between them.
+
+// One edge tile. Its bytes go one by one: no alignment is asked of src or
+// tile.
+struct PatchEdge {
+  const void* src;      // the first NEW byte of this tile
+  void* tile;           // the tile's first byte in the pool
+  uint32_t lo, hi;      // the new bytes take [lo, hi) of the tile, lo < hi <= valid
+  uint32_t valid;       // bytes of the tile that exist: 1024, less only in the
+                        // last tile of the object (which is its shard's last too)
+  uint64_t shard_tile, obj_tile;  // the tile, counted in its shard / its object
+  uint32_t shard, obj;            // indices into the shard / object arrays
+};
+static_assert(sizeof(PatchEdge) % 8 == 0);
+
+// INVALID_ARGUMENT unless, for every edge: the indices are in range; the tile
+// exists in its shard and in its object and valid is what both leave of it
+// (min(1024, length − tile·1024), the same counted either way);
+// lo < hi <= valid; [src, src+hi−lo) does not overlap [tile, tile+valid); and
+// no run and no other edge of the same shard covers the tile (wave order
+// would decide which old term is subtracted). The runs must have passed
+// check_patch_geometry.
+inline Result<void> check_patch_edges(const PatchEdge* edges, uint32_t nedge,
+                                      const PatchSeg* segs, uint32_t nseg,
+                                      const uint64_t* shard_lens,
+                                      uint32_t nshard,
+                                      const uint64_t* obj_sizes,
+                                      uint32_t nobj) {
+  using digest::kTileBytes;
+  if (nedge == 0) return {};
+  auto bad = [](uint32_t i, const char* what) {
+    return Error{ErrorCode::INVALID_ARGUMENT,
+                 "patch edge " + std::to_string(i) + ": " + what};
+  };
+  // (shard, first tile, tile count) of the non-empty runs and of the edges
+  std::vector<std::tuple<uint32_t, uint64_t, uint64_t>> runs, tiles;
+  for (uint32_t i = 0; i < nseg; ++i)
+    if (segs[i].nbytes != 0)
+      runs.emplace_back(segs[i].shard, segs[i].shard_tile,
+                        (segs[i].nbytes + kTileBytes - 1) / kTileBytes);
+  std::sort(runs.begin(), runs.end());
+  // bytes of tile t that exist in `len` bytes; 0: the tile does not
+  auto left = [](uint64_t len, uint64_t t) -> uint64_t {
+    if (t > len / kTileBytes) return 0;
+    return std::min<uint64_t>(kTileBytes, len - t * kTileBytes);
+  };
+  for (uint32_t i = 0; i < nedge; ++i) {
+    const PatchEdge& e = edges[i];
+    if (e.shard >= nshard) return bad(i, "shard index out of range");
+    if (e.obj >= nobj) return bad(i, "object index out of range");
+    const uint64_t in_shard = left(shard_lens[e.shard], e.shard_tile);
+    const uint64_t in_obj = left(obj_sizes[e.obj], e.obj_tile);
+    if (in_shard == 0) return bad(i, "tile past its shard");
+    if (in_obj == 0) return bad(i, "tile past its object");
+    if (e.valid != in_shard || e.valid != in_obj)
+      return bad(i, "valid is not what its shard and object leave of the tile");
+    if (e.lo >= e.hi || e.hi > e.valid) return bad(i, "not lo < hi <= valid");
+    const uint64_t a = reinterpret_cast<uint64_t>(e.src);
+    const uint64_t b = reinterpret_cast<uint64_t>(e.tile);
+    const uint64_t n = e.hi - e.lo;
+    if (n > ~a || e.valid > ~b) return bad(i, "address range wraps");
+    if (a < b + e.valid && b < a + n) return bad(i, "source overlaps its tile");
+    // the last run that starts at or before the tile
+    auto it = std::upper_bound(
+        runs.begin(), runs.end(),
+        std::make_tuple(e.shard, e.shard_tile, ~uint64_t{0}));
+    if (it != runs.begin()) {
+      const auto& [rs, rt, rn] = *(it - 1);
+      if (rs == e.shard && e.shard_tile < rt + rn)
+        return bad(i, "lies on a tile of a run");
+    }
+    tiles.emplace_back(e.shard, e.shard_tile, i);
+  }
+  std::sort(tiles.begin(), tiles.end());
+  for (size_t k = 1; k < tiles.size(); ++k)
+    if (std::get<0>(tiles[k - 1]) == std::get<0>(tiles[k]) &&
+        std::get<1>(tiles[k - 1]) == std::get<1>(tiles[k]))
+      return bad(static_cast<uint32_t>(std::get<2>(tiles[k])),
+                 "lies on the tile of another edge");
+  return {};
+}
+
+// An edge before it has addresses.
+struct EdgePiece {
+  uint32_t shard;       // index into the copy's shards
+  uint64_t shard_tile;  // the tile, counted in the shard
+  uint64_t obj_tile;    // ... and in the object
+  uint32_t lo, hi, valid;
+  uint64_t src_off;     // where the tile's new bytes begin in the caller's
+};
+
+struct BytePatchPlan {
+  std::vector<RangePiece> runs;  // whole tiles (or to the object's end)
+  std::vector<EdgePiece> edges;
+};
+
+// plan_patch at byte granularity: [offset, offset+length) of one copy as
+// whole-tile runs, each a legal PatchSeg once it has addresses, plus the edge
+// tiles at the range's head and tail. Shards start on tile boundaries of their
+// object, so only the first piece can have a head edge and only the last a
+// tail edge: at most two edges. A range that ends at the object's end ends in
+// a run (the tail path the runs have), not in an edge, unless it also starts
+// inside that tile. For every range plan_patch accepts this is plan_patch's
+// pieces and no edge. nullopt: plan_stripe refuses the copy, or the range
+// leaves the object.
+inline std::optional<BytePatchPlan> plan_patch_bytes(
+    uint64_t obj_size, const std::vector<uint64_t>& shard_lens, uint64_t offset,
+    uint64_t length) {
+  using digest::kTileBytes;
+  if (!plan_stripe(obj_size, shard_lens)) return std::nullopt;
+  auto pieces = range_pieces(obj_size, shard_lens, offset, length);
+  if (!pieces) return std::nullopt;
+  BytePatchPlan out;
+  for (const RangePiece& p : *pieces) {
+    const uint64_t slen = shard_lens[p.shard];
+    const uint64_t shard_base = p.obj_off - p.shard_off;  // a tile boundary
+    uint64_t a = p.shard_off;
+    const uint64_t e = p.shard_off + p.nbytes;
+    auto edge = [&](uint64_t from, uint64_t to) {  // inside one tile
+      const uint64_t t = from / kTileBytes;
+      out.edges.push_back(
+          {p.shard, t, (shard_base + from) / kTileBytes,
+           static_cast<uint32_t>(from - t * kTileBytes),
+           static_cast<uint32_t>(to - t * kTileBytes),
+           static_cast<uint32_t>(std::min(kTileBytes, slen - t * kTileBytes)),
+           shard_base + from - offset});
+    };
+    if (a % kTileBytes != 0) {  // head
+      const uint64_t stop =
+          std::min(e, (a / kTileBytes + 1) * uint64_t{kTileBytes});
+      edge(a, stop);
+      a = stop;
+    }
+    if (a == e) continue;
+    const bool to_end = shard_base + e == obj_size;
+    const uint64_t run_end = to_end ? e : e - e % kTileBytes;
+    if (a < run_end)
+      out.runs.push_back({p.shard, a, shard_base + a, run_end - a});
+    if (run_end < e) edge(run_end, e);  // tail
+  }
+  return out;
+}
+
 }  // namespace blackbird::gpu
